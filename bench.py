@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """reward-pairs/sec of the HIP scoring path (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A "step" = one custom_forward over one batch of 32 synthetic (caption, image) rows per GPU
@@ -9,7 +9,11 @@ A "step" = one custom_forward over one batch of 32 synthetic (caption, image) ro
 tokens, 128-token caption, S = 2642) followed by the all-gather of the rewards (the only
 collective of the path).  Weak scaling: rows per GPU fixed.
 Inputs are resident in HBM before the timed region.  Weights: seeded synthetic (no checkpoint exists
-offline); rank 0 at N=1 also times the CPU oracle on a bounded sample (cpu_baseline).
+offline).  A plain run sets up, warms up, times the steps and prints the result line, nothing else;
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (same arguments, same
+inputs); --full adds everything else the benchmark measures: the live golden sweep (parity_check),
+the dominant-kernel roofline probe, the secondary legs and, rank 0 at N=1, the CPU oracle on a
+bounded sample (cpu_baseline).
 """
 import argparse
 import json
@@ -30,6 +34,22 @@ FLOP_PER_PAIR = 26.86e12          # algorithmic 2*MAC per (capti
 PEAK_TFLOPS = 2500.0              # dense bf16/f16 MFMA, MI355X_MICROARCH.md "Chip-level parameters"
 
 
+def usable_cpus():
+    """CPUs this process may run on: its affinity mask, capped by a cgroup v2 CPU quota and by OMP_NUM_THREADS where either is set
+    (os.cpu_count() is the whole host's, and a thread pool sized by it on a quota-limited share only slows itself down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def cpu_baseline(cfg_full):
     """Time the CPU oracle (oracle/phi3v_reward_oracle.py, kind 'port') on the GPU box's host cores: ONE row of the headline
     workload at full shapes and FULL depth (17 crops x 23 CLIP layers, S = 2642 x 32 decoder layers, SkipCA, value head), fp32
@@ -39,7 +59,7 @@ def cpu_baseline(cfg_full):
     from llava_reward_amd import synth
     from oracle import phi3v_reward_oracle as orc
     g = torch.Generator().manual_seed(0)
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     probe_a, probe_w = torch.randn(2642, 3072, generator=g), torch.randn(16384, 3072, generator=g)
     best = (1e9, ncpu)
     for nt in sorted({ncpu, max(1, ncpu // 2), max(1, ncpu // 4), min(ncpu, 32)}):
@@ -64,7 +84,8 @@ def cpu_baseline(cfg_full):
     total = time.time() - t0
     assert torch.isfinite(r).all()
     # how it scales with rows and threads (SURVEY.md §8d asks for B = 1 and B = 2): the same pipeline at full SHAPES and reduced
-    # DEPTH (2 of 23 CLIP layers, 2 of 32 decoder layers: a bounded sample), B = 1 and 2, at 32 / 64 / 128 threads
+    # DEPTH (2 of 23 CLIP layers, 2 of 32 decoder layers: a bounded sample), B = 1 and 2, at 32 / 64 / 128 threads (those of them
+    # this process has CPUs for; all of its CPUs where it has fewer than 32)
     import dataclasses
     cfg_s = dataclasses.replace(cfg_full, layers=2, clip=dataclasses.replace(cfg_full.clip, layers_used=2))
     Ws = {k: v for k, v in W.items() if not re.search(r"layers\.([2-9]|[1-9]\d)\.", k)}
@@ -72,20 +93,18 @@ def cpu_baseline(cfg_full):
     for B in (1, 2):
         bb = synth.synth_batch(cfg_s, 1234, [128] * B, (4, 4), with_pixels=False)
         pp = torch.randn(B, 17, 3, 336, 336, generator=g)
-        for nt in (32, 64, 128):
-            if nt > ncpu:
-                continue
+        for nt in sorted({t for t in (32, 64, 128) if t <= ncpu} or {ncpu}):
             torch.set_num_threads(nt)
             t1 = time.time()
             orc.custom_forward(Ws, cfg_s, bb["input_ids"], bb["attention_mask"], pp, bb["image_sizes"])
             scaling.append({"rows": B, "threads": nt, "seconds": time.time() - t1})
     torch.set_num_threads(threads)
-    return {"value": 1.0 / total, "unit": "reward-pairs/sec", "cores": threads, "host_cpus": ncpu, "kind": "port",
+    return {"value": 1.0 / total, "unit": "reward-pairs/sec", "cores": threads, "host_cpus": os.cpu_count() or 1, "usable_cpus": ncpu, "kind": "port",
             "seconds_per_row": total,
             "cores_note": f"{threads} = the thread count that ran a decoder-sized GEMM fastest on this host (probed over {sorted({ncpu, max(1, ncpu // 2), max(1, ncpu // 4), min(ncpu, 32)})}), not the host's CPU count",
             "thread_scaling_sample": {"what": "same pipeline, full shapes, 2 CLIP + 2 decoder layers", "runs": scaling},
             "sample": f"1 row at full shapes and full depth (17 crops x {cfg_full.clip.layers_used} CLIP layers, S={batch['input_ids'].shape[1]} x "
-                      f"{cfg_full.layers} decoder layers), measured end to end ({total:.1f}s), fp32 torch, {threads} threads of {ncpu} host CPUs"}
+                      f"{cfg_full.layers} decoder layers), measured end to end ({total:.1f}s), fp32 torch, {threads} threads on {ncpu} usable of {os.cpu_count()} host CPUs"}
 
 
 def qwen_flop_per_row(cfg, grid, S):
@@ -429,8 +448,12 @@ def main():
                     help="bt = BASELINE configs[1] (BT head, B=32): the metric; gpm_pairwise = configs[2]: GPM head d=2 + SkipCA, a step = chosen and "
                          "rejected forward of B=64 rows each + preference_compute (reports preference-pairs/s beside reward-pairs/s)")
     ap.add_argument("--lora-rank", type=int, default=0, help="run the main workload with an un-merged rank-r adapter on the decoder linears")
-    ap.add_argument("--quick", action="store_true", help="main line only: no secondary legs and no golden sweep -- only the timed workload's "
-                                                          "launches (plus the dominant-kernel probe's) reach a profiler")
+    ap.add_argument("--full", action="store_true", help="besides the timed workload: the live golden sweep, the dominant-kernel roofline probe, "
+                                                         "the secondary legs and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                                                                          "(rank 0, all ranks' rows) as DIR/<name>.npy, float32")
+    ap.add_argument("--quick", action="store_true", help="with --full: main line only, no secondary legs and no golden sweep -- only the timed "
+                                                          "workload's launches (plus the dominant-kernel probe's) reach a profiler")
     ap.add_argument("--no-golden", action="store_true", help="skip the live golden sweep (parity_check)")
     ap.add_argument("--profile-run", action="store_true", help="for rocprofv3 runs (tools/profile_round.sh): --quick, and NOTHING but the timed workload's "
                     "launches reaches the profiler -- no operand-form probe at .to('cuda') (the default form is pinned: what the probe locks on these "
@@ -453,6 +476,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU smoke tests)")
     ap.add_argument("--all-ranks-on-device", type=int, default=-1, help="smoke test: put every rank on this one GPU")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.profile_run:
         a.quick = True
 
@@ -587,18 +612,21 @@ def main():
     pargs = type("A", (), dict(is_general_preference=cfg.is_general_preference, value_head_dim=cfg.value_head_dim,
                                general_preference_tau=cfg.general_preference_tau))
 
+    last = {}          # what the latest step handed its caller, by name (--dump-outputs)
+
     def step():
         r = forward(model, w)
         if pairwise:       # eval/batch_inference_rm_phi.py:92-108: chosen forward, rejected forward, preference probability
             rr = forward(model, w, pix_r)
             if world > 1:
                 r, rr = (gather_rewards(r), gather_rewards(rr)) if a.backend == "nccl" else (gather_rewards(r.cpu()), gather_rewards(rr.cpu()))
-            return torch.from_numpy(preference_compute(pargs, r, rr))
-        if world == 1:
-            return r
-        if a.backend != "nccl":               # gloo smoke path: collectives on host tensors
-            return gather_rewards(r.cpu())
-        return gather_rewards(r)
+            p = torch.from_numpy(preference_compute(pargs, r, rr))
+            last.update(chosen_rewards=r, rejected_rewards=rr, preference=p)
+            return p
+        if world > 1:
+            r = gather_rewards(r.cpu()) if a.backend != "nccl" else gather_rewards(r)      # (gloo smoke path: collectives on host tensors)
+        last.update(rewards=r)
+        return r
 
     for _ in range(a.warmup):
         out = step()
@@ -614,6 +642,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:       # the last timed step's results as its caller received them (a few KB: no sampling needed)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, t in last.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
     multi = None
     if world > 1:
         cdev = "cuda" if a.backend == "nccl" else "cpu"
@@ -672,7 +704,7 @@ def main():
             res["preference_pairs_per_sec"] = world * B * a.steps / dt
             res["config"]["step"] = "chosen forward + rejected forward (B rows each) + preference_compute (GPM d=2 formula)"
         headline = a.model == "phi3v" and a.num_crops == 16 and not pairwise and not a.lora_rank
-        if world == 1:
+        if world == 1 and a.full:
             full = (a.model != "phi3v" or a.num_crops == 16) and not a.lora_rank      # the golden rows: 17-crop images, no adapter
             res["parity_check"] = golden_check(model, a.model, current=(1234, main_profile)) if (full and not a.quick and not a.no_golden) else None
             if a.model == "phi3v" and a.num_crops == 16 and not a.profile_run:
@@ -684,7 +716,7 @@ def main():
                                         "note": res["roofline"]["note"] + "; achieved/frac = the dominant kernel (algorithmic FLOPs per launch / HIP-event "
                                                 "time, measured by this run); traffic / mfma_busy / clock_ghz = PMC figures of the committed rocprofv3 summary, null "
                                                 "unless its recorded kernel sources are this build's; whole_pass = the same ratio for the step"})
-        if world == 1 and not a.quick:
+        if world == 1 and a.full and not a.quick:
             # the same step with the pixel hand-over included: fp32 pixels start in pinned host memory (what the processor
             # returns) and cross PCIe on the forward's stream every step.  Reported beside `value`, never as `value`.
             sub_steps = min(a.steps, 3)
@@ -858,7 +890,10 @@ def main():
                 res["fast_mode"] = fm
             if headline and not a.no_cpu_baseline:
                 res["cpu_baseline"] = cpu_baseline(cfg)
-        emit(res)
+        if a.full:
+            emit(res)
+        else:
+            print(compact_line(res), flush=True)     # a plain run: the result line alone, no legs file
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

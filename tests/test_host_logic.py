@@ -431,6 +431,17 @@ def test_bench_final_line_is_compact_and_last(tmp_path, capsys):
     assert len(bench.compact_line(res)) <= bench.LINE_BUDGET
 
 
+def test_bench_options_without_a_gpu():
+    """bench.py offers --full and --dump-outputs, and refuses a step count that would time nothing before it touches a GPU."""
+    import subprocess
+    import sys
+    bench = [sys.executable, os.path.join(ROOT, "bench.py")]
+    h = subprocess.run(bench + ["--help"], capture_output=True, text=True, timeout=300)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    r = subprocess.run(bench + ["--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_form_ladder_and_loader_knobs_without_a_gpu():
     """Host side of the operand-form machinery (round 5): the probe's candidate ladder (cheapest first, strict from the front of the
     model in eighths of the decoder), the pin-only single-pass tails, the constructor's validation, and the loader's pass-through of the

@@ -22,4 +22,4 @@ bash tools/pmc_step.sh $TAG/pmc_step > $O/${TAG}_pmc_step.md 2>&1; python3 tools
 bash tools/pmc_run.sh $TAG/pmc "mixed" 2>&1 | tail -3; cp $O/pmc/pmc_gemm_gate_up.json $O/${TAG}_pmc_gemm_gate_up.json
 bash tools/pmc_attn.sh $TAG/pmc_attn 2>&1 | tail -12 | tee $O/${TAG}_pmc_attention.md
 rm -rf $O/kstats_* $O/pmc/mixed/*/ $O/pmc_attn/*/ $O/pmc_step/*/
-(cd $R && python3 bench.py --steps 8 --warmup 2 > $O/bench.log 2>&1); grep '^{' $O/bench.log | tail -1 > $O/${TAG}_bench.json; cp gpurun_out/bench_legs.json $O/${TAG}_bench_legs.json; cut -c1-600 $O/${TAG}_bench.json
+(cd $R && python3 bench.py --full --steps 8 --warmup 2 > $O/bench.log 2>&1); grep '^{' $O/bench.log | tail -1 > $O/${TAG}_bench.json; cp $(dirname $O)/bench_legs.json $O/${TAG}_bench_legs.json; cut -c1-600 $O/${TAG}_bench.json
