@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LR_ABI_VERSION 9
+#define LR_ABI_VERSION 10
 
 enum { LR_OK = 0, LR_EINVAL = 1, LR_EHIP = 2, LR_ESTATE = 3, LR_ENOTFOUND = 4, LR_ENOMEM = 5 };
 enum { LR_DT_BF16 = 0, LR_DT_F16 = 1, LR_DT_F32 = 2 };
@@ -259,6 +259,11 @@ int lr_op_attention_split_ex(const void* Q, const void* K, const void* V, void* 
 int lr_op_attention_segments(const void* Q, const void* K, const void* V, void* O, const int32_t* cu_seqlens_host, int n_seg,
                              int ldq, int ldo, int qoff, int koff, int voff, int heads, int head_dim, float scale,
                              int operand_dtype, void* hip_stream);
+/* ... in split-operand form (ABI 10): Q/K/V rows carry their residuals lo_off columns to the right, O is stored [O_hi | O_lo] when
+ * o_split > 0, the softmax reference maximum as in lr_op_attention_split_ex (what the Qwen2.5-VL ViT runs in split-operand stages). */
+int lr_op_attention_segments_split(const void* Q, const void* K, const void* V, void* O, const int32_t* cu_seqlens_host, int n_seg,
+                                   int ldq, int ldo, int qoff, int koff, int voff, int lo_off, int o_split, int heads, int head_dim,
+                                   float scale, float lazy_threshold, int operand_dtype, void* hip_stream);
 /* W8A8 mode: rows of an operand-typed matrix -> OCP e4m3 bytes q [rows, K] + one fp32 scale per row (max|x| / 448), and
  * C = epilogue((A8 W8^T) * ascale[m] * wscale[n]) on v_mfma_scale_f32_16x16x128_f8f6f4; K multiple of 128. */
 int lr_op_quantize_rows_fp8(const void* x, int rows, int K, int ldx, void* q, float* scale, int operand_dtype, void* hip_stream);

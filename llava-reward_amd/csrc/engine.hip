@@ -946,28 +946,44 @@ int lr_op_attention_split_ex(const void* Q, const void* K, const void* V, void* 
     });
 }
 
+// ragged launch over host cu_seqlens: one work item per (segment, 128-query tile); S = the longest segment (the 8192-key limit applies)
+static void attention_segments(AttnParams p, const int32_t* cu, int n_seg, int head_dim, int operand_dtype, hipStream_t st) {
+    if (!cu || n_seg < 1) throw std::invalid_argument("attention_segments: need at least one segment");
+    std::vector<int4> items;
+    int max_len = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        const int len = cu[i + 1] - cu[i];
+        if (len < 0) throw std::invalid_argument("attention_segments: cu_seqlens must be non-decreasing");
+        for (int q = 0; q * 128 < len; ++q) items.push_back(make_int4(cu[i], len, q, 0));
+        max_len = std::max(max_len, len);
+    }
+    if (items.empty()) return;
+    int4* d_items = nullptr;
+    LR_HIP_CHECK(hipMalloc((void**)&d_items, items.size() * sizeof(int4)));
+    LR_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    p.S = max_len; p.kv_group = 1; p.items = d_items; p.n_items = (int)items.size();
+    try { launch_attention(p, 1, head_dim, false, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, st); }
+    catch (...) { hipStreamSynchronize(st); hipFree(d_items); throw; }
+    LR_HIP_CHECK(hipStreamSynchronize(st));
+    LR_HIP_CHECK(hipFree(d_items));
+}
+
 int lr_op_attention_segments(const void* Q, const void* K, const void* V, void* O, const int32_t* cu, int n_seg, int ldq, int ldo,
                              int qoff, int koff, int voff, int heads, int head_dim, float scale, int operand_dtype, void* hip_stream) {
     return op_guard([&] {
-        if (!cu || n_seg < 1) throw std::invalid_argument("attention_segments: need at least one segment");
-        std::vector<int4> items;
-        int max_len = 0;
-        for (int i = 0; i < n_seg; ++i) {
-            const int len = cu[i + 1] - cu[i];
-            if (len < 0) throw std::invalid_argument("attention_segments: cu_seqlens must be non-decreasing");
-            for (int q = 0; q * 128 < len; ++q) items.push_back(make_int4(cu[i], len, q, 0));
-            max_len = std::max(max_len, len);
-        }
-        if (items.empty()) return;
-        int4* d_items = nullptr;
-        LR_HIP_CHECK(hipMalloc((void**)&d_items, items.size() * sizeof(int4)));
-        hipStream_t st = (hipStream_t)hip_stream;
-        LR_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-        AttnParams p{Q, K, V, O, nullptr, nullptr, 0, ldq, ldo, qoff, koff, voff, max_len, heads, scale, 1, d_items, (int)items.size()};
-        try { launch_attention(p, 1, head_dim, false, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, st); }
-        catch (...) { hipStreamSynchronize(st); hipFree(d_items); throw; }
-        LR_HIP_CHECK(hipStreamSynchronize(st));
-        LR_HIP_CHECK(hipFree(d_items));
+        AttnParams p{Q, K, V, O, nullptr, nullptr, 0, ldq, ldo, qoff, koff, voff, 0, heads, scale, 1};
+        attention_segments(p, cu, n_seg, head_dim, operand_dtype, (hipStream_t)hip_stream);
+    });
+}
+
+int lr_op_attention_segments_split(const void* Q, const void* K, const void* V, void* O, const int32_t* cu, int n_seg, int ldq,
+                                   int ldo, int qoff, int koff, int voff, int lo_off, int o_split, int heads, int head_dim, float scale,
+                                   float lazy_threshold, int operand_dtype, void* hip_stream) {
+    return op_guard([&] {
+        if (lo_off <= 0) throw std::invalid_argument("attention_segments_split: lo_off must be positive");
+        AttnParams p{Q, K, V, O, nullptr, nullptr, 0, ldq, ldo, qoff, koff, voff, 0, heads, scale, 1, nullptr, 0, lo_off, o_split};
+        p.lazy_t = lazy_threshold;
+        attention_segments(p, cu, n_seg, head_dim, operand_dtype, (hipStream_t)hip_stream);
     });
 }
 
