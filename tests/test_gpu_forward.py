@@ -5,7 +5,7 @@ reference itself (tests/golden/ref_*.json), including the FULL-SIZE Phi-3.5-V ca
 weights are regenerated in HBM by the same integer hash the golden script used.
 
 Tolerance (north star): |reward - reference fp32 CPU reward| <= 1e-3.  The default, split-operand mode
-("f16x2": activations as f16 hi + lo, bf16-valued weights exact in f16) is held to 1e-4 everywhere,
+("f16x2": activations as f16 hi + lo, bf16-valued weights exact in f16 from 2^-14 up) is held to 1e-4 everywhere,
 full-size rows included (measured <= 1.5e-5).  The single-pass fast modes are noise-limited: "f16"
 meets 1e-3 on the small configs and lands within 1e-3 in the assert_close sense (atol = rtol) on the
 full-size rows; "bf16" (the reference's own GPU dtype) is held to 8e-3.
