@@ -70,6 +70,10 @@ struct VitLayer {              // Qwen2_5_VLVisionBlock
     float *qkv_b, *proj_b, *gu_b, *down_b, *n1, *n2;
 };
 
+// Operand form of a stage or site: prec = split operands ([hi | lo] buffers, twice as wide), lo8 = ... with the residual pass of the
+// big GEMMs in e4m3 (desc.precise == 2).  Passed to the producer and the consumer launched for a site; never a state.
+struct Form { int prec, lo8; };
+
 struct lr_engine {
     lr_model_desc d;
     int device = 0;
@@ -93,19 +97,15 @@ struct lr_engine {
     int Hq = 0, Hkv = 0, Nqkv = 0;      // decoder projection widths: heads*hd, kv_heads*hd, Hq + 2*Hkv
     bool llava = false, qwen = false;
     int op_dt = DT_BF16;
-    int prec = 0;              // split-operand mode: operand buffers are [hi | lo], twice as wide
-    int lo8 = 0;               // ... with the residual pass of the big GEMMs in e4m3 (desc.precise == 2)
+    Form created{0, 0};        // the form the handle was created with (desc.precise): sizes every buffer; written by lr_create only
     // block scales of one-byte residuals (common.h lo8_scale_at): two arrays used in turn -- a GEMM reads its operand's scales from
     // one while its epilogue writes its output's into the other -- and the row exponents of the e4m3 copy of a hi half
     unsigned char* sc[2] = {nullptr, nullptr}; size_t sc_cap = 0; int sc_i = 0;
-    const unsigned char* pre_enc_sc = nullptr;       // the scale array that belongs to pre_enc
     int* aexp2 = nullptr; size_t aexp2_cap = 0;
     unsigned* amax_word = nullptr;
     std::unordered_map<const void*, int> w8exp;      // weight base pointer -> E8M0 exponent of its prepared e4m3 twin
     std::unordered_map<const void*, int> w8exp2;     // ... and of e4m3(W_lo) for weights that are inexact in the operand type
     void* w8tmp = nullptr; size_t w8tmp_cap = 0;
-    const void* pre_enc = nullptr;                   // operand buffer whose residual half its producer has already written in e4m3
-    bool pre_enc_hi8 = false;                        // ... together with the e4m3 copy of its hi half (third e4m3 segment)
     std::unordered_map<const void*, void*> own8;     // adapter A matrices: weight base pointer -> its e4m3 twin in a buffer of its own
     // weights that are NOT exact in the operand type: their rows [e4m3(W) | e4m3(W_lo)] live in a buffer of their own, so that the
     // 16-bit residuals stay intact in the residual twin and the handle can still run the strict form (lr_set_precision_map)
@@ -169,7 +169,7 @@ struct lr_engine {
     int* sched_mem = nullptr;                        // tile-scheduler words of this engine's persistent GEMM launches (GemmParams::sched_mem)
     // precision map (lr_set_precision_map): operand form per stage, -1 = the descriptor's.  0 single pass, 1 split (16-bit residuals),
     // 2 split with e4m3 residual passes.  Decoder layers [pm_first, layers - pm_last) take pm_mid, the others the descriptor's form.
-    int prec0 = 0, lo8_0 = 0, pm_clip = -1, pm_mid = -1, pm_first = 0, pm_last = 0;
+    int pm_clip = -1, pm_mid = -1, pm_first = 0, pm_last = 0;
     // ... and per SITE of a decoder layer in that range (lr_set_precision_sites, round 6): -1 = the layer's form.  A site = an operand
     // producer together with the GEMM (or attention launch) that reads it, so a site's form never crosses into its neighbours'.
     enum : int { SITE_QKV = 0, SITE_ATTN = 1, SITE_O = 2, SITE_GATE_UP = 3, SITE_DOWN = 4, N_SITES = 5 };
@@ -177,9 +177,10 @@ struct lr_engine {
     // lazy reference maximum of the attention launches in DEFAULT-form stages (lr_set_attention_lazy_threshold; log2 units, 0 = exact).
     // Strict stages run the exact maximum (att_lazy_t_strict = 0) except in the probe's noise-floor pass (model.py _compare_forms).
     float att_lazy_t = ATT_LAZY_T_DEFAULT, att_lazy_t_strict = 0.f;
-    void set_form(int m) { if (m < 0) { prec = prec0; lo8 = lo8_0; } else { prec = m ? 1 : 0; lo8 = m == 2 ? 1 : 0; } pre_enc = nullptr; }
+    Form form(int m) const { return m < 0 ? created : Form{m ? 1 : 0, m == 2 ? 1 : 0}; }
     int layer_form(int l) const { return (pm_mid >= 0 && l >= pm_first && l < d.layers - pm_last) ? pm_mid : -1; }
     int site_form(int l, int site) const { const int f = layer_form(l); return (f >= 0 && pm_site[site] >= 0) ? pm_site[site] : f; }
+    Form site(int l, int s) const { return form(site_form(l, s)); }
 
     void* dalloc(size_t bytes, bool weight) {
         void* p = nullptr;
@@ -218,7 +219,7 @@ inline void add_slot(lr_engine* e, const std::string& name, std::vector<int64_t>
     else { s.rows = (int)shape[0]; int64_t c = 1; for (size_t i = 1; i < shape.size(); ++i) c *= shape[i]; s.cols = (int)c; }
     s.dst = dst; s.ld_dst = ld_dst; s.cols_dst = cols_dst; s.dst_dtype = dst_dtype; s.mode = mode;
     s.std_ = std_; s.offset = offset;
-    if (e->prec && (dst_dtype == DT_F16 || dst_dtype == DT_BF16)) {
+    if (e->created.prec && (dst_dtype == DT_F16 || dst_dtype == DT_BF16)) {
         for (size_t i = 0; i < e->wbufs.size(); ++i) {
             const lr_engine::WBuf& w = e->wbufs[i];
             if ((char*)dst >= w.hi && (char*)dst < w.hi + w.bytes) { s.lo_dst = w.lo + ((char*)dst - w.hi); s.wid = (int)i; break; }
@@ -231,7 +232,7 @@ inline void add_slot(lr_engine* e, const std::string& name, std::vector<int64_t>
 inline float* falloc(lr_engine* e, size_t n) { return (float*)e->dalloc(n * 4, true); }
 inline void* oalloc(lr_engine* e, size_t n) {
     void* hi = e->dalloc(n * 2, true);
-    if (e->prec) {
+    if (e->created.prec) {
         void* lo = e->dalloc(n * 2, true);
         e->wbuf_of[hi] = (int)e->wbufs.size();
         e->wbufs.push_back({(char*)hi, (char*)lo, n * 2});
@@ -312,15 +313,36 @@ template <typename F> int guarded(lr_engine* e, F&& f) {
     }
 }
 
+// An activation buffer as the GEMM or attention launch behind it reads it.  Producers (norms, im2col and the gathers, operand-out /
+// SwiGLU / RoPE epilogues, the in-place re-encode) return or fill one; consumers take one and refuse a layout their form does not read.
+enum : int { LAY_SINGLE = 0, LAY_LO16 = 1, LAY_LO8 = 2 };      // rows of `width` | [hi | 16-bit lo] | [hi | block-scaled e4m3 lo]
+struct Operand {
+    void* p = nullptr;
+    int width = 0, rows = 0;               // LOGICAL columns (the consumer's K) and rows
+    int lay = LAY_SINGLE;
+    const unsigned char* sc = nullptr;     // LAY_LO8: the block scales of the residual half (one of lr_engine::sc)
+    bool hi8 = false;                      // LAY_LO8: ... together with the e4m3 copy of the hi half (third e4m3 segment, lr_engine::aexp2)
+    int ld() const { return lay == LAY_SINGLE ? width : 2 * width; }
+};
+// what every producer without a one-byte residual path writes at form f
+inline Operand operand16(void* p, int width, int rows, Form f) { return Operand{p, width, rows, f.prec ? LAY_LO16 : LAY_SINGLE}; }
+// A consumer at form f reads single rows or [hi | lo] rows, nothing else: a site override (lr_set_precision_sites) on a single-pass
+// layer range would otherwise have a single-pass reader walk [hi | lo] rows at half their stride, silently.
+inline void check_layout(const Operand& x, Form f, const char* reader) {
+    if ((x.lay != LAY_SINGLE) != (f.prec != 0))
+        throw std::logic_error(std::string(reader) + (f.prec ? ": a split-operand site reads single rows" : ": a single-pass site reads [hi | lo] rows") +
+                               " (lr_set_precision_map / lr_set_precision_sites: neighbouring sites must agree on split operands)");
+}
+
 // Split-operand mode: callers pass LOGICAL shapes; here A becomes [A_hi | A_lo] (K doubled, W re-read from column 0) and an
 // operand-typed output becomes [C_hi | C_lo].
 // With desc.precise == 2 the residual pass of a GEMM that runs on the deep-pipelined kernel is made in e4m3: the residual half of
-// A arrives as block-scaled e4m3 from its producer (norms, SwiGLU / operand-out epilogues: pre_enc) or is re-encoded in place
+// A arrives as block-scaled e4m3 from its producer (norms, SwiGLU / operand-out epilogues: LAY_LO8) or is re-encoded in place
 // (stream-ordered, right here: every operand buffer feeds exactly one GEMM after it is produced), and W's e4m3 twin is prepared on
 // first use in the rows of its residual buffer (exact weights only; one synchronisation per weight).
-// apply_prec_base only rewrites the parameters (no side effects); upgrade_lo8 commits the e4m3 form right before the launch.
-inline void apply_prec_base(const lr_engine* e, GemmParams& p) {
-    if (!e->prec) return;
+// apply_prec_base only rewrites the parameters (no side effects); commit_lo8 commits the e4m3 form right before the launch.
+inline void apply_prec_base(const lr_engine* e, Form f, GemmParams& p) {
+    if (!f.prec) return;
     p.kw = p.K; p.K *= 2; p.lda *= 2;
     auto it = e->wbuf_of.find(p.W);
     if (it != e->wbuf_of.end() && !e->inexact.empty() && e->inexact[it->second]) {     // weights not exact in the operand type
@@ -331,8 +353,8 @@ inline void apply_prec_base(const lr_engine* e, GemmParams& p) {
 }
 // The choice must not depend on M: a row's reward has to be bit-identical whatever else is in the batch (sharding across GPUs
 // must not change a preference), so every eligible GEMM takes this form -- on the deep-pipelined kernel -- at any row count.
-inline bool lo8_eligible(const lr_engine* e, const GemmParams& p) {      // p after apply_prec_base
-    if (!e->lo8 || p.kw <= 0) return false;
+inline bool lo8_eligible(const lr_engine* e, Form f, const GemmParams& p) {      // p after apply_prec_base
+    if (!f.lo8 || p.kw <= 0) return false;
     if (e->wbuf_of.find(p.W) == e->wbuf_of.end()) return false;
     const bool aligned = p.N % 8 == 0 && p.ldc % 8 == 0 && (((uintptr_t)p.C) & 15) == 0 && (!p.bias || (((uintptr_t)p.bias) & 15) == 0);
     return aligned && p.kw % 128 == 0 && p.ldw == p.kw && (e->gemm_tile < 0 || e->gemm_tile == 6);
@@ -384,61 +406,42 @@ inline void ensure_aexp(lr_engine* e, size_t rows, size_t K) {
 // the array the next producer of one-byte residuals writes its scales to
 inline unsigned char* next_scales(lr_engine* e) { e->sc_i ^= 1; return e->sc[e->sc_i]; }
 
-// keep_enc: another GEMM reads the same operand buffer next (the main GEMM behind an adapter's t GEMM): leave the "already encoded"
-// mark on it.  force_hi8: that next GEMM needs the e4m3 copy of the hi half as well, so the one in-place encoding pass writes it now.
-inline void upgrade_lo8(lr_engine* e, GemmParams& p, hipStream_t st, bool keep_enc = false, bool force_hi8 = false) {
-    if (p.aexp) return;
-    if (lo8_eligible(e, p)) {
-        // Weights inexact in the operand type (Wlo set by apply_prec_base: a merged LoRA adapter, fp32-trained weights): a third
-        // e4m3 segment, A_hi8 x e4m3(W_lo)^T, replaces the 16-bit [x_hi] x [W_lo] segment (2x instead of 3x the single pass).
-        // Adapter matrices (own8) keep the 16-bit third segment: their e4m3 twin lives in a buffer of its own.
-        const bool inexact = p.Wlo != nullptr;
-        auto own = e->own8.find(p.W);
-        const bool third8 = inexact && own == e->own8.end();
-        const bool hi8 = third8 || force_hi8;
-        auto it = e->wbuf_of.find(p.W);
-        char* lo_rows = e->wbufs[it->second].lo;
-        ensure_lo8_twin(e, p.W, p.N, p.kw, p.ldw, st);
-        auto w8 = e->w8exp.find(p.W);
-        ensure_aexp(e, (size_t)p.M, (size_t)p.kw);
-        int* aexp2 = e->aexp2;
-        if (!(e->pre_enc == p.A && (!hi8 || e->pre_enc_hi8))) {
-            if (e->pre_enc == p.A) throw std::logic_error("operand buffer already carries e4m3 residuals without the e4m3 copy of its hi half");
-            unsigned char* sc = next_scales(e);
-            launch_quantize_lo_inplace(const_cast<void*>(p.A), p.lda, p.kw, p.M, sc, e->op_dt, st, hi8 ? aexp2 : nullptr);
-            e->pre_enc_hi8 = hi8;
-            e->pre_enc_sc = sc;
-        }
-        p.aexp = e->pre_enc_sc;
-        e->pre_enc = keep_enc ? p.A : nullptr;      // (a norm kernel may have written [hi | e4m3(lo)] and the scales itself: lo8_norm_target)
-        if (own != e->own8.end()) { p.Wlo16 = inexact ? lo_rows : nullptr; p.Wlo = own->second; }
-        else if (inexact) p.Wlo = e->pair8.at(p.W);
-        else p.Wlo = lo_rows;
-        p.wexp = w8->second;
-        p.aexp2 = third8 ? aexp2 : nullptr;
-        p.wexp2 = e->w8exp2[p.W];
-    }
-}
-inline void apply_prec(lr_engine* e, GemmParams& p, hipStream_t st) {
-    apply_prec_base(e, p);
-    upgrade_lo8(e, p, st);
-}
-// For a norm kernel that feeds the GEMM described by `probe` (logical shapes, as passed to gemm()): where to put the block scales if
-// that GEMM will take the e4m3 residual form with exact weights, else null (the norm then writes 16-bit residuals as usual).
-inline unsigned char* lo8_norm_target(lr_engine* e, GemmParams probe) {
-    e->pre_enc = nullptr;
-    if (!e->lo8) return nullptr;
-    apply_prec_base(e, probe);
-    if (!lo8_eligible(e, probe) || probe.Wlo) return nullptr;
-    ensure_aexp(e, (size_t)probe.M, (size_t)probe.kw);
-    e->pre_enc = probe.A;
-    e->pre_enc_hi8 = false;
+// x's residual half as block-scaled e4m3 (hi8: with the e4m3 copy of its hi half): nothing to do on rows that carry them already, else
+// one in-place pass.  Idempotent, so the adapter's t GEMM and the main GEMM, which read the same rows, both call it.
+inline void encode_lo8(lr_engine* e, Operand& x, bool hi8, hipStream_t st) {
+    if (x.lay == LAY_LO8 && (!hi8 || x.hi8)) return;
+    if (x.lay == LAY_LO8) throw std::logic_error("operand buffer already carries e4m3 residuals without the e4m3 copy of its hi half");
     unsigned char* sc = next_scales(e);
-    e->pre_enc_sc = sc;
-    return sc;
+    launch_quantize_lo_inplace(x.p, x.ld(), x.width, x.rows, sc, e->op_dt, st, hi8 ? e->aexp2 : nullptr);
+    x.lay = LAY_LO8; x.sc = sc; x.hi8 = hi8;
 }
-inline void apply_prec(const lr_engine* e, AttnParams& p) {
-    if (!e->prec) return;
+// p: after apply_prec_base, lo8_eligible, reading x.  next_hi8: the GEMM that reads the same rows next (the main GEMM behind an
+// adapter's t GEMM) needs the e4m3 copy of the hi half, so the one in-place encoding pass writes it now.
+inline void commit_lo8(lr_engine* e, GemmParams& p, Operand& x, hipStream_t st, bool next_hi8 = false) {
+    // Weights inexact in the operand type (Wlo set by apply_prec_base: a merged LoRA adapter, fp32-trained weights): a third
+    // e4m3 segment, A_hi8 x e4m3(W_lo)^T, replaces the 16-bit [x_hi] x [W_lo] segment (2x instead of 3x the single pass).
+    // Adapter matrices (own8) keep the 16-bit third segment: their e4m3 twin lives in a buffer of its own.
+    const bool inexact = p.Wlo != nullptr;
+    auto own = e->own8.find(p.W);
+    const bool third8 = inexact && own == e->own8.end();
+    char* lo_rows = e->wbufs[e->wbuf_of.find(p.W)->second].lo;
+    ensure_lo8_twin(e, p.W, p.N, p.kw, p.ldw, st);
+    ensure_aexp(e, (size_t)p.M, (size_t)p.kw);
+    encode_lo8(e, x, third8 || next_hi8, st);
+    p.aexp = x.sc;
+    if (own != e->own8.end()) { p.Wlo16 = inexact ? lo_rows : nullptr; p.Wlo = own->second; }
+    else if (inexact) p.Wlo = e->pair8.at(p.W);
+    else p.Wlo = lo_rows;
+    p.wexp = e->w8exp.find(p.W)->second;
+    p.aexp2 = third8 ? e->aexp2 : nullptr;
+    p.wexp2 = e->w8exp2[p.W];
+}
+// An attention launch at form f reading q, k, v from the rows of `qkv` (p in LOGICAL strides); returns O as the GEMM behind it reads it.
+inline Operand apply_prec(const lr_engine* e, Form f, AttnParams& p, const Operand& qkv, int o_rows) {
+    check_layout(qkv, f, "attention");
+    if (qkv.lay == LAY_LO8) throw std::logic_error("attention reads 16-bit residuals: its operand carries e4m3 residuals");
+    const Operand o = operand16(p.O, p.ldo, o_rows, f);
+    if (!f.prec) return o;
     p.lo_off = p.ldq; p.ldq *= 2;
     p.o_split = p.ldo; p.ldo *= 2;
     // strict stages (16-bit residual passes: the probe's yardstick, and what an amplifying weight set is locked to) keep the exact
@@ -446,7 +449,8 @@ inline void apply_prec(const lr_engine* e, AttnParams& p) {
     // (A/B switches for tools/outlier_fp64_probe.py, read once: LR_ATT_LAZY_T overrides the default-form stages' threshold, LR_ATT_LAZY_T_STRICT the strict stages')
     static const float t_def = [] { const char* v = getenv("LR_ATT_LAZY_T"); return v ? (float)atof(v) : -1.f; }();
     static const float t_strict = [] { const char* v = getenv("LR_ATT_LAZY_T_STRICT"); return v ? (float)atof(v) : 0.f; }();
-    p.lazy_t = e->lo8 ? (t_def >= 0.f ? t_def : e->att_lazy_t) : (t_strict > 0.f ? t_strict : e->att_lazy_t_strict);
+    p.lazy_t = f.lo8 ? (t_def >= 0.f ? t_def : e->att_lazy_t) : (t_strict > 0.f ? t_strict : e->att_lazy_t_strict);
+    return o;
 }
 
 // W8A8 mode: quantise the rows of A, make sure W has its e4m3 twin, launch the e4m3 form.  Like lo8_eligible, the choice never
@@ -470,10 +474,10 @@ inline void ensure_q8(lr_engine* e, size_t rows, size_t K) {
 // synchronise or allocate (weights re-uploaded afterwards fall back to preparation at their first launch).
 struct GemmWeight { const void* W; int N, K; size_t rows; };
 inline void prepare_twins(lr_engine* e, const std::vector<GemmWeight>& ws) {
-    if (!e->lo8 && !e->w8a8) return;
+    if (!e->created.lo8 && !e->w8a8) return;
     for (const GemmWeight& g : ws) {
         if (!g.W || g.K % 128) continue;
-        if (e->lo8) { ensure_lo8_twin(e, g.W, g.N, g.K, g.K, 0); ensure_aexp(e, g.rows, (size_t)g.K); }
+        if (e->created.lo8) { ensure_lo8_twin(e, g.W, g.N, g.K, g.K, 0); ensure_aexp(e, g.rows, (size_t)g.K); }
         else { ensure_w8a8_twin(e, g.W, g.N, g.K, g.K, 0); ensure_q8(e, g.rows, (size_t)g.K); }
     }
     LR_HIP_CHECK(hipStreamSynchronize(0));
@@ -491,71 +495,93 @@ inline bool launch_w8a8(lr_engine* e, GemmParams p, hipStream_t st) {
     return true;
 }
 
-// For a GEMM whose operand-typed output C [M, Kout] is read next by the GEMM with weight next_W [next_N, Kout]: where the producer's
-// epilogue should put C's block scales if that consumer will take the e4m3 residual form with exact weights (it then finds its
-// operand encoded: no in-place pass), else null.  p: the producer after apply_prec (its kernel must be the deep-pipelined one).
-inline unsigned char* lo8_out_target(lr_engine* e, const GemmParams& p, const void* next_W, int next_N) {
-    if (!e->lo8 || !next_W || p.split <= 0 || !(p.epi == EPI_OUT_OP || p.epi == EPI_SWIGLU_OP)) return nullptr;
-    if (!(p.A2 || gemm_bt_is_deep(p, e->gemm_tile)) || (e->gemm_tile >= 0 && e->gemm_tile != 6)) return nullptr;
-    const int Kout = p.split;                                  // logical output columns = the consumer's K
-    GemmParams probe{p.C, next_W, nullptr, nullptr, p.M, next_N, Kout, Kout, Kout, next_N, EPI_OUT_F32, ACT_NONE, nullptr, 0, 0};
-    apply_prec_base(e, probe);
-    if (!lo8_eligible(e, probe) || probe.Wlo) return nullptr;
-    ensure_aexp(e, (size_t)p.M, (size_t)Kout);
-    return next_scales(e);
-}
-inline void mark_lo8_out(lr_engine* e, const GemmParams& p) {
-    if (!p.oexp) return;
-    e->pre_enc = p.C;
-    e->pre_enc_hi8 = false;
-    e->pre_enc_sc = p.oexp;
+// One linear layer y = act(x W^T + bias), described ONCE, in LOGICAL shapes: the same object tells the producer of x whether to write
+// one-byte residuals (lo8_scales) and launches the GEMM (linear() below), so the two cannot disagree about the rows between them.
+struct Linear {
+    const void* W; const float* bias; int N, K;      // W [N, K]
+    int epi, act;
+    const Lora* L = nullptr;               // un-merged adapter, or null / k2 == 0
+    const float* rope_cs = nullptr; int rope_cols = 0, rope_hd = 0;     // EPI_ROPE_OP (GemmParams)
+    bool adapter() const { return L && L->k2 > 0; }
+    bool rope_tiles_ok() const { return rope_cols % 256 == 0; }        // the fused RoPE epilogue rotates whole 256-column tiles
+    int out_cols() const { return epi == EPI_SWIGLU_OP ? N / 2 : N; }
+    GemmParams params(const lr_engine* e, const void* A, void* C, int M) const {
+        GemmParams p{A, W, C, bias, M, N, K, K, K, out_cols(), epi, act, rope_cs, rope_cols, rope_hd};
+        p.sched_mem = e->sched_mem;
+        return p;
+    }
+    // For the producer of this GEMM's operand x [M, K] (a norm kernel, the epilogue of the GEMM in front): where to put x's block
+    // scales if this GEMM, at form f, will take the e4m3 residual form with exact weights (it then finds its operand encoded: no
+    // in-place pass), else null (the producer writes 16-bit residuals as usual).
+    unsigned char* lo8_scales(lr_engine* e, Form f, int M) const {
+        if (!f.lo8 || (epi == EPI_ROPE_OP && !rope_tiles_ok())) return nullptr;       // (no fused RoPE: qkv_rope runs another GEMM)
+        GemmParams probe = params(e, nullptr, nullptr, M);
+        apply_prec_base(e, f, probe);
+        if (!lo8_eligible(e, f, probe) || probe.Wlo) return nullptr;
+        ensure_aexp(e, (size_t)M, (size_t)K);
+        return next_scales(e);
+    }
+};
+
+// y = norm(x) as the operand of `reader` at form f (reader == null: 16-bit residuals whatever reads them).
+inline Operand norm_rows(lr_engine* e, hipStream_t st, Form f, const Linear* reader, const float* x, const float* w, const float* b, void* y,
+                         int rows, int H, float eps, int group = 1) {
+    Operand o = operand16(y, H * group, rows / group, f);
+    unsigned char* sc = reader ? reader->lo8_scales(e, f, o.rows) : nullptr;
+    launch_norm_rows(x, w, b, y, rows, H, eps, e->op_dt, st, f.prec, group, sc);
+    if (sc) { o.lay = LAY_LO8; o.sc = sc; }
+    return o;
 }
 
-// One linear layer, p in LOGICAL shapes (as gemm() takes them).  With an adapter L: t = x A^T first (always on the deep-pipelined
-// kernel, in the same operand form as the main GEMM -- they read the same rows of x), then the main GEMM with the K-extension.
-// next_W / next_N: the weight of the GEMM that reads this one's output as its operand (lo8_out_target), or null.
-// next_form: the operand form of the site that reads this GEMM's output (lr_engine::site_form), -2 = the form in force now: decides
-// whether the epilogue writes one-byte residuals (lo8_out_target looks at the CONSUMER's form, not at this GEMM's).
-inline unsigned char* lo8_out_target_for(lr_engine* e, const GemmParams& p, const void* next_W, int next_N, int next_form) {
-    if (next_form == -2) return lo8_out_target(e, p, next_W, next_N);
-    const int sp = e->prec, sl = e->lo8;
-    if (next_form < 0) { e->prec = e->prec0; e->lo8 = e->lo8_0; } else { e->prec = next_form ? 1 : 0; e->lo8 = next_form == 2 ? 1 : 0; }
-    unsigned char* t = (e->prec == sp) ? lo8_out_target(e, p, next_W, next_N) : nullptr;      // (a single-pass neighbour: no residual half at all)
-    e->prec = sp; e->lo8 = sl;
-    return t;
-}
-inline void gemm_p(lr_engine* e, hipStream_t st, GemmParams p, const Lora* L = nullptr, const void* next_W = nullptr, int next_N = 0, int next_form = -2) {
-    p.sched_mem = e->sched_mem;
-    if (L && L->k2 > 0) {
+// Runs l on the rows of x at form f, C = the output buffer; returns the output as its reader finds it (operand-typed epilogues).
+// With an adapter: t = x A^T first (always on the deep-pipelined kernel, in the same operand form as the main GEMM -- they read the
+// same rows of x), then the main GEMM with the K-extension.
+// next / next_f: the linear that reads this one's output as its operand and the form of ITS site (default: f): they decide whether the
+// epilogue writes one-byte residuals -- the CONSUMER's form and weights, not this GEMM's.  The kernel must be the deep-pipelined one.
+inline Operand linear(lr_engine* e, hipStream_t st, Form f, const Linear& l, Operand& x, void* C, const Linear* next = nullptr, Form next_f = Form{-1, -1}) {
+    check_layout(x, f, "GEMM");
+    if (next_f.prec < 0) next_f = f;
+    const bool op_out = l.epi == EPI_OUT_OP || l.epi == EPI_SWIGLU_OP || l.epi == EPI_ROPE_OP;
+    Operand y = op_out ? operand16(C, l.out_cols(), x.rows, f) : Operand{};
+    GemmParams p = l.params(e, x.p, C, x.rows), t{};
+    if (l.adapter()) {
         if (e->w8a8) throw std::logic_error("W8A8 mode runs merged weights only (no un-merged adapters)");
-        GemmParams probe = p;
-        apply_prec_base(e, probe);
-        GemmParams t{p.A, L->A, e->lt, nullptr, p.M, L->k2, p.K, p.lda, p.K, L->k2, EPI_OUT_OP, ACT_NONE, nullptr, 0, 0};
-        t.sched_mem = e->sched_mem;
-        apply_prec_base(e, t);
-        const bool both8 = lo8_eligible(e, probe) && lo8_eligible(e, t);
-        if (e->pre_enc == p.A && !both8) throw std::logic_error("operand pre-encoded in e4m3 for a GEMM that takes the 16-bit form");
-        if (both8) upgrade_lo8(e, t, st, true, probe.Wlo != nullptr);
-        launch_gemm_bt(t, e->op_dt, 6, st);
-        p.A2 = e->lt; p.lda2 = L->k2 * (1 + e->prec); p.W2 = L->B; p.ldw2 = L->k2; p.k2 = L->k2;
-        auto it = e->wbuf_of.find(L->B);
+        const int k2 = l.L->k2;
+        t = Linear{l.L->A, nullptr, k2, l.K, EPI_OUT_OP, ACT_NONE}.params(e, x.p, e->lt, x.rows);
+        apply_prec_base(e, f, t);
+        p.A2 = e->lt; p.lda2 = k2 * (1 + f.prec); p.W2 = l.L->B; p.ldw2 = k2; p.k2 = k2;
+        auto it = e->wbuf_of.find(l.L->B);
         if (it != e->wbuf_of.end() && !e->inexact.empty() && e->inexact[it->second]) p.W2lo = e->wbufs[it->second].lo;
-        apply_prec_base(e, p);
-        if (both8) upgrade_lo8(e, p, st);
-        p.oexp = lo8_out_target_for(e, p, next_W, next_N, next_form);
-        launch_gemm_bt(p, e->op_dt, e->gemm_tile, st);
-        mark_lo8_out(e, p);
-        return;
+    } else if (launch_w8a8(e, p, st)) return y;
+    apply_prec_base(e, f, p);
+    const bool lo8 = lo8_eligible(e, f, p) && (!l.adapter() || lo8_eligible(e, f, t));
+    if (x.lay == LAY_LO8 && !lo8) throw std::logic_error("operand pre-encoded in e4m3 for a GEMM that takes the 16-bit form");
+    if (l.adapter()) {
+        if (lo8) commit_lo8(e, t, x, st, p.Wlo != nullptr);
+        launch_gemm_bt(t, e->op_dt, 6, st);
     }
-    if (launch_w8a8(e, p, st)) return;
-    apply_prec(e, p, st);
-    p.oexp = lo8_out_target_for(e, p, next_W, next_N, next_form);
+    if (lo8) commit_lo8(e, p, x, st);
+    if (next && next_f.prec == f.prec && (l.epi == EPI_OUT_OP || l.epi == EPI_SWIGLU_OP) && p.split > 0 &&        // (a single-pass neighbour: no residual half at all)
+        (p.A2 || gemm_bt_is_deep(p, e->gemm_tile)) && (e->gemm_tile < 0 || e->gemm_tile == 6))
+        p.oexp = next->lo8_scales(e, next_f, p.M);
     launch_gemm_bt(p, e->op_dt, e->gemm_tile, st);
-    mark_lo8_out(e, p);
+    if (p.oexp) { y.lay = LAY_LO8; y.sc = p.oexp; }
+    return y;
 }
-inline void gemm(lr_engine* e, hipStream_t st, const void* A, const void* W, void* C, const float* bias, int M, int N, int K, int lda,
-          int ldw, int ldc, int epi, int act, const Lora* L = nullptr, const void* next_W = nullptr, int next_N = 0, int next_form = -2) {
-    gemm_p(e, st, GemmParams{A, W, C, bias, M, N, K, lda, ldw, ldc, epi, act, nullptr, 0, 0}, L, next_W, next_N, next_form);
+
+// qkv projection with RoPE on q, k (l: EPI_ROPE_OP; v = the columns behind rope_cols): fused in the GEMM epilogue when the
+// deep-pipelined kernel runs, else an fp32 projection + launch_rope_split.
+// qkv32: the pre-RoPE fp32 projections of up to cap_rows rows: only the fallback needs them, so they are allocated on its first use
+// (decoder: 3.1 GB at B = 32).
+inline Operand qkv_rope(lr_engine* e, hipStream_t st, Form f, const Linear& l, Operand& x, void* qkv, float*& qkv32, size_t cap_rows) {
+    GemmParams probe = l.params(e, x.p, qkv, x.rows);
+    apply_prec_base(e, f, probe);
+    if (l.rope_tiles_ok() && (l.adapter() || w8a8_eligible(e, probe) || lo8_eligible(e, f, probe) || gemm_bt_is_deep(probe, e->gemm_tile)))
+        return linear(e, st, f, l, x, qkv);
+    if (!qkv32) qkv32 = (float*)e->dalloc((cap_rows + 256) * l.N * 4, false);
+    linear(e, st, f, Linear{l.W, l.bias, l.N, l.K, EPI_OUT_F32, ACT_NONE, l.L}, x, qkv32);
+    launch_rope_split(qkv32, l.rope_cs, qkv, x.rows, l.rope_cols, l.N - l.rope_cols, l.rope_hd, e->op_dt, st, f.prec);
+    return operand16(qkv, l.N, x.rows, f);
 }
 
 // Adapter slots of one linear `mod` (checkpoint names mod.lora_A.weight [r, K], mod.lora_B.weight [n_rows, r]); part / parts: this
@@ -568,7 +594,7 @@ inline void register_lora(lr_engine* e, Lora& L, const std::string& mod, int N_f
         L.k2 = parts * rp;
         L.A = oalloc(e, (size_t)L.k2 * K);
         L.B = oalloc(e, (size_t)N_fused * L.k2);
-        if (e->lo8) e->own8[L.A] = e->dalloc((size_t)L.k2 * K * 2, true);
+        if (e->created.lo8) e->own8[L.A] = e->dalloc((size_t)L.k2 * K * 2, true);
         e->lora_k2max = std::max(e->lora_k2max, L.k2);
     }
     add_slot(e, mod + ".lora_A.weight", {r, K}, (char*)L.A + (size_t)part * rp * K * 2, K, K, od, PACK_PLAIN, 0.02, 0);

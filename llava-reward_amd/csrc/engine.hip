@@ -186,7 +186,7 @@ void validate_desc(const lr_model_desc& d) {
 // Qwen2_5_VLDecoderLayer (q/k/v bias).  RoPE comes from the per-token (cos, sin) table h->cs.
 void alloc_gather_ws(lr_engine* h) {
     const lr_model_desc& d = h->d;
-    const size_t R = (size_t)d.max_batch + 256, ob = 2 * (size_t)(1 + h->prec);
+    const size_t R = (size_t)d.max_batch + 256, ob = 2 * (size_t)(1 + h->created.prec);
     h->xg = (float*)h->dalloc(R * d.hidden * 4, false);
     h->hg = h->dalloc(R * d.hidden * ob, false);
     h->attg = h->dalloc(R * h->Hq * ob, false);
@@ -195,83 +195,60 @@ void alloc_gather_ws(lr_engine* h) {
 
 // DIAGNOSTIC ONLY (LR_ATT_EMU_LO8=1; tools/dbg/attn_lo8_probe.py): round the K / V residuals the attention kernel is about to read to
 // e4m3 with one scale per (token, head) -- see launch_emulate_lo8.  No effect unless the variable is set; default form only.
-static void emulate_attention_lo8(lr_engine* h, const AttnParams& ap, size_t rows, int kv_heads, int hd, hipStream_t st) {
+static void emulate_attention_lo8(lr_engine* h, Form f, const AttnParams& ap, size_t rows, int kv_heads, int hd, hipStream_t st) {
     static const bool on = [] { const char* e = getenv("LR_ATT_EMU_LO8"); return e && atoi(e) != 0; }();
-    if (!on || !ap.lo_off || !h->lo8) return;          // (stages in the default form only: lo8 = the e4m3-residual form is in force)
+    if (!on || !ap.lo_off || !f.lo8) return;          // (stages in the default form only: f.lo8 = the e4m3-residual form)
     launch_emulate_lo8((void*)ap.K, rows, ap.ldq, ap.lo_off + ap.koff, kv_heads, hd, h->op_dt, st);
     launch_emulate_lo8((void*)ap.V, rows, ap.ldq, ap.lo_off + ap.voff, kv_heads, hd, h->op_dt, st);
 }
 
+// Second half of decoder layer l on the att.rows rows of att (the attention output): o_proj and gate_up / down, each added to the
+// residual stream x; hn / ff: the operand buffers of the post-attention norm and of the SwiGLU output.  The full pass and the gathered
+// last layer run this one copy: the GEMM kernels never look at M when they pick their form.
+static void decoder_tail(lr_engine* h, hipStream_t st, int l, Operand att, float* x, void* hn, void* ff) {
+    const lr_model_desc& d = h->d;
+    const DecLayer& L = h->dl[l];
+    const int D = d.hidden, I = d.intermediate;
+    const Form fo = h->site(l, lr_engine::SITE_O), fg = h->site(l, lr_engine::SITE_GATE_UP), fd = h->site(l, lr_engine::SITE_DOWN);
+    const Linear o{L.o_w, nullptr, D, h->Hq, EPI_RESADD_F32, ACT_NONE, &L.lo}, gu{L.gu_w, nullptr, 2 * I, D, EPI_SWIGLU_OP, ACT_NONE, &L.lgu},
+                 down{L.down_w, nullptr, D, I, EPI_RESADD_F32, ACT_NONE, &L.ldown};
+    linear(h, st, fo, o, att, x);
+    Operand n = norm_rows(h, st, fg, &gu, x, L.ln2, nullptr, hn, att.rows, D, d.rms_eps);
+    Operand f = linear(h, st, fg, gu, n, ff, &down, fd);      // ff is down's operand: its residual format is chosen for THAT site
+    linear(h, st, fd, down, f, x);
+}
+
 bool run_decoder_stack(lr_engine* h, hipStream_t st, const int64_t* attention_mask, int B, int S, int gather) {
     const lr_model_desc& d = h->d;
-    const int D = d.hidden, I = d.intermediate, Rl = B * S;
+    const int D = d.hidden, Rl = B * S;
     const int nl = h->lim_layers >= 0 && h->lim_layers < d.layers ? h->lim_layers : d.layers;
     const float ascale = 1.0f / std::sqrt((float)h->hd);
     const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
-    bool pruned = false;
     for (int l = 0; l < nl; ++l) {
         const DecLayer& L = h->dl[l];
-        // the operand form of every site of this layer (lr_set_precision_map / lr_set_precision_sites); set right in front of the
-        // site's producer, in force until its consumer has been launched
-        auto site = [&](int s) { h->set_form(h->site_form(l, s)); };
-        site(lr_engine::SITE_QKV);
-        {   // qkv projection with RoPE on q,k: fused in the GEMM epilogue when the deep-pipelined kernel runs
-            GemmParams gp{h->h, L.qkv_w, h->qkv, L.qkv_b, Rl, Nqkv, D, D, D, Nqkv, EPI_ROPE_OP, ACT_NONE, h->cs, Hq + Hkv, h->hd};
-            const bool tiles_ok = (Hq + Hkv) % 256 == 0;
-            launch_norm_rows(h->x, L.ln1, nullptr, h->h, Rl, D, d.rms_eps, h->op_dt, st, h->prec, 1, tiles_ok ? lo8_norm_target(h, gp) : nullptr);
-            GemmParams probe = gp;
-            apply_prec_base(h, probe);
-            if (tiles_ok && (L.lqkv.k2 > 0 || w8a8_eligible(h, probe) || lo8_eligible(h, probe) || gemm_bt_is_deep(probe, h->gemm_tile))) {
-                gemm_p(h, st, gp, &L.lqkv);
-            } else {
-                // (pre-RoPE fp32 projections: only this fallback needs them, so the 3.1 GB at B=32 are allocated on its first use)
-                if (!h->qkv32) h->qkv32 = (float*)h->dalloc(((size_t)d.max_batch * d.max_seq + 256) * Nqkv * 4, false);
-                gemm(h, st, h->h, L.qkv_w, h->qkv32, L.qkv_b, Rl, Nqkv, D, D, D, Nqkv, EPI_OUT_F32, ACT_NONE, &L.lqkv);
-                launch_rope_split(h->qkv32, h->cs, h->qkv, Rl, Hq + Hkv, Hkv, h->hd, h->op_dt, st, h->prec);
-            }
-        }
+        // the operand form of every site of this layer (lr_set_precision_map / lr_set_precision_sites): handed to the site's
+        // producer and to its consumer
+        const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
+        const Linear qkv{L.qkv_w, L.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &L.lqkv, h->cs, Hq + Hkv, h->hd};
+        Operand n = norm_rows(h, st, fq, &qkv, h->x, L.ln1, nullptr, h->h, Rl, D, d.rms_eps);
+        const Operand q = qkv_rope(h, st, fq, qkv, n, h->qkv, h->qkv32, (size_t)d.max_batch * d.max_seq);
         AttnParams ap{h->qkv, h->qkv, h->qkv, h->att, attention_mask, h->tstat + 1, 4, Nqkv, Hq, 0, Hq, Hq + Hkv, S, d.heads, ascale,
                       d.heads / d.kv_heads};
-        if (gather && l == nl - 1) {
-            // Last layer: every row still feeds K and V, but only one row per sequence is read afterwards (rw_model:408-421).  Its
-            // query sits in the qkv rows as usual; the attention kernel runs the one query tile that holds it (same arithmetic as
-            // in the full launch) and stores B rows; the residual rows are gathered and o_proj / norm / MLP run on M = B rows --
-            // the GEMM kernels never look at M when they pick their form, so these rows come out bit-identical to a full layer.
-            ap.O = h->attg;
-            ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = gather == 2 ? 1 : 0;
-            site(lr_engine::SITE_ATTN);
-            apply_prec(h, ap);
-            emulate_attention_lo8(h, ap, Rl, d.kv_heads, h->hd, st);
-            launch_attention(ap, B, h->hd, true, h->op_dt, st);
-            launch_gather_norm_rows(h->x, h->tstat, S, gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);      // (no weight: a plain row gather)
-            site(lr_engine::SITE_O);
-            gemm(h, st, h->attg, L.o_w, h->xg, nullptr, B, D, Hq, Hq, Hq, D, EPI_RESADD_F32, ACT_NONE, &L.lo);
-            site(lr_engine::SITE_GATE_UP);
-            launch_norm_rows(h->xg, L.ln2, nullptr, h->hg, B, D, d.rms_eps, h->op_dt, st, h->prec, 1,
-                             lo8_norm_target(h, GemmParams{h->hg, L.gu_w, h->ffg, nullptr, B, 2 * I, D, D, D, I, EPI_SWIGLU_OP, ACT_NONE, nullptr, 0, 0}));
-            gemm(h, st, h->hg, L.gu_w, h->ffg, nullptr, B, 2 * I, D, D, D, I, EPI_SWIGLU_OP, ACT_NONE, &L.lgu, L.down_w, D, h->site_form(l, lr_engine::SITE_DOWN));
-            { const void* enc = h->pre_enc; const unsigned char* esc = h->pre_enc_sc; const bool e8 = h->pre_enc_hi8;
-              site(lr_engine::SITE_DOWN); h->pre_enc = enc; h->pre_enc_sc = esc; h->pre_enc_hi8 = e8; }      // (ffg's residual format was chosen for THIS site: keep its mark)
-            gemm(h, st, h->ffg, L.down_w, h->xg, nullptr, B, D, I, I, I, D, EPI_RESADD_F32, ACT_NONE, &L.ldown);
-            pruned = true;
-            break;
-        }
-        site(lr_engine::SITE_ATTN);
-        apply_prec(h, ap);
-        emulate_attention_lo8(h, ap, Rl, d.kv_heads, h->hd, st);
+        // Last layer: every row still feeds K and V, but only one row per sequence is read afterwards (rw_model:408-421).  Its
+        // query sits in the qkv rows as usual; the attention kernel runs the one query tile that holds it (same arithmetic as
+        // in the full launch) and stores B rows; the residual rows are gathered and o_proj / norm / MLP run on M = B rows --
+        // the GEMM kernels never look at M when they pick their form, so these rows come out bit-identical to a full layer.
+        const bool pruned = gather && l == nl - 1;
+        if (pruned) { ap.O = h->attg; ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = gather == 2 ? 1 : 0; }
+        const Operand att = apply_prec(h, fa, ap, q, pruned ? B : Rl);
+        emulate_attention_lo8(h, fa, ap, Rl, d.kv_heads, h->hd, st);
         launch_attention(ap, B, h->hd, true, h->op_dt, st);
-        site(lr_engine::SITE_O);
-        gemm(h, st, h->att, L.o_w, h->x, nullptr, Rl, D, Hq, Hq, Hq, D, EPI_RESADD_F32, ACT_NONE, &L.lo);
-        site(lr_engine::SITE_GATE_UP);
-        launch_norm_rows(h->x, L.ln2, nullptr, h->h, Rl, D, d.rms_eps, h->op_dt, st, h->prec, 1,
-                         lo8_norm_target(h, GemmParams{h->h, L.gu_w, h->ff, nullptr, Rl, 2 * I, D, D, D, I, EPI_SWIGLU_OP, ACT_NONE, nullptr, 0, 0}));
-        gemm(h, st, h->h, L.gu_w, h->ff, nullptr, Rl, 2 * I, D, D, D, I, EPI_SWIGLU_OP, ACT_NONE, &L.lgu, L.down_w, D, h->site_form(l, lr_engine::SITE_DOWN));      // ff is down's operand
-        { const void* enc = h->pre_enc; const unsigned char* esc = h->pre_enc_sc; const bool e8 = h->pre_enc_hi8;
-          site(lr_engine::SITE_DOWN); h->pre_enc = enc; h->pre_enc_sc = esc; h->pre_enc_hi8 = e8; }
-        gemm(h, st, h->ff, L.down_w, h->x, nullptr, Rl, D, I, I, I, D, EPI_RESADD_F32, ACT_NONE, &L.ldown);
+        if (!pruned) { decoder_tail(h, st, l, att, h->x, h->h, h->ff); continue; }
+        launch_gather_norm_rows(h->x, h->tstat, S, gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);      // (no weight: a plain row gather)
+        decoder_tail(h, st, l, att, h->xg, h->hg, h->ffg);
+        return true;
     }
-    h->set_form(-1);
-    return pruned;
+    return false;
 }
 
 void alloc_mean_pool(lr_engine* h, size_t rows, size_t vcap) {
@@ -331,8 +308,7 @@ int lr_create(const lr_model_desc* desc, int device, lr_handle* out) {
         e->d = *desc;
         e->device = device;
         e->op_dt = desc->operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16;
-        e->prec = e->prec0 = desc->precise ? 1 : 0;
-        e->lo8 = e->lo8_0 = desc->precise == 2 ? 1 : 0;
+        e->created = Form{desc->precise ? 1 : 0, desc->precise == 2 ? 1 : 0};
         e->sched_mem = (int*)e->dalloc(64, true);
         e->w8a8 = desc->w8a8 ? 1 : 0;
         e->llava = desc->backbone == LR_BACKBONE_LLAVA_NEXT;
@@ -495,7 +471,7 @@ int lr_finalize(lr_handle h) {
         const size_t PAD = 256;
         const size_t NC = B * C, Rc = NC * h->T + PAD, Rp = NC * (h->T - 1) + PAD, SV = B * (size_t)h->Vcap + PAD, Rl = B * S + PAD;
         auto W = [&](size_t bytes) { return h->dalloc(bytes, false); };
-        const size_t ob = 2 * (size_t)(1 + h->prec);      // bytes per operand element (hi [+ lo])
+        const size_t ob = 2 * (size_t)(1 + h->created.prec);      // bytes per operand element (hi [+ lo])
         h->patchA = W(Rp * h->Kpad * ob); h->patch_out = (float*)W(Rp * Hc * 4);
         h->clip_x = (float*)W(Rc * Hc * 4); h->clip_h = W(Rc * Hc * ob); h->clip_qkv = W(Rc * 3 * Hc * ob);
         h->clip_att = W(Rc * Hc * ob); h->clip_ff = W(Rc * Mc * ob);
@@ -550,7 +526,7 @@ int lr_set_layer_limits(lr_handle h, int n_clip_layers, int n_layers) {
 int lr_set_precision_map(lr_handle h, int clip_form, int decoder_mid_form, int decoder_first, int decoder_last) {
     if (!h) return LR_EINVAL;
     return guarded(h, [&] {
-        auto ok = [&](int m) { return m >= -1 && m <= 2 && (m <= 0 || (h->prec0 && h->op_dt == DT_F16) || (m == 1 && h->prec0)) && (m != 2 || h->lo8_0); };
+        auto ok = [&](int m) { return m >= -1 && m <= 2 && (m <= 0 || (h->created.prec && h->op_dt == DT_F16) || (m == 1 && h->created.prec)) && (m != 2 || h->created.lo8); };
         if (!ok(clip_form) || !ok(decoder_mid_form) || decoder_first < 0 || decoder_last < 0)
             throw std::invalid_argument("lr_set_precision_map: a stage can take form 0, or a split form the handle was created with "
                                         "(precise >= 1 for form 1, precise == 2 for form 2)");
@@ -562,7 +538,7 @@ int lr_set_precision_sites(lr_handle h, int qkv_form, int attention_form, int o_
     return guarded(h, [&] {
         const int f[lr_engine::N_SITES] = {qkv_form, attention_form, o_proj_form, gate_up_form, down_form};
         for (int v : f)
-            if (v != -1 && !(v == 1 && h->prec0) && !(v == 2 && h->lo8_0))
+            if (v != -1 && !(v == 1 && h->created.prec) && !(v == 2 && h->created.lo8))
                 throw std::invalid_argument("lr_set_precision_sites: a site takes -1 (the layer's form), 1 (16-bit residual passes; handle created with "
                                             "precise >= 1) or 2 (e4m3 residual passes; precise == 2)");
         for (int i = 0; i < lr_engine::N_SITES; ++i) h->pm_site[i] = f[i];
@@ -598,7 +574,7 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
         if (n_crops < 2 || n_crops > d.max_crops) throw std::invalid_argument("lr_forward: n_crops exceeds max_crops");
         if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_forward: pixel dtype must be F32 or BF16");
         hipStream_t st = (hipStream_t)hip_stream;
-        const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, I = d.intermediate, T = h->T, g2 = h->G / 2;
+        const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, T = h->T, g2 = h->G / 2;
         const int img = d.clip_image;
 
         // ---- host plan: active crops, per-sample vision geometry, image-token offsets ----
@@ -666,39 +642,42 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
 
         // ---- CLIP tower (utils/utils.py:266-273) ----
         const int Rp = NC * (T - 1), Rc = NC * T;
-        h->set_form(h->pm_clip);
-        launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, img, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, h->prec);
-        gemm(h, st, h->patchA, h->patch_w, h->patch_out, nullptr, Rp, Hc, h->Kpad, h->Kpad, h->Kpad, Hc, EPI_OUT_F32, ACT_NONE);
+        const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision stage's operand form (covers the projector)
+        launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, img, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, fv.prec);
+        Operand pa = operand16(h->patchA, h->Kpad, Rp, fv);
+        linear(h, st, fv, Linear{h->patch_w, nullptr, Hc, h->Kpad, EPI_OUT_F32, ACT_NONE}, pa, h->patch_out);
         launch_clip_embed(h->patch_out, h->cls, h->pos, h->pre_w, h->pre_b, h->clip_x, NC, T, Hc, d.clip_ln_eps, st);
         const int ncl = h->lim_clip >= 0 && h->lim_clip < d.clip_layers ? h->lim_clip : d.clip_layers;
         for (int l = 0; l < ncl; ++l) {
             const ClipLayer& c = h->cl[l];
-            launch_norm_rows(h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps, h->op_dt, st, h->prec, 1,
-                             lo8_norm_target(h, GemmParams{h->clip_h, c.qkv_w, h->clip_qkv, c.qkv_b, Rc, 3 * Hc, Hc, Hc, Hc, 3 * Hc, EPI_OUT_OP, ACT_NONE, nullptr, 0, 0}));
-            gemm(h, st, h->clip_h, c.qkv_w, h->clip_qkv, c.qkv_b, Rc, 3 * Hc, Hc, Hc, Hc, 3 * Hc, EPI_OUT_OP, ACT_NONE);
+            const Linear qkv{c.qkv_w, c.qkv_b, 3 * Hc, Hc, EPI_OUT_OP, ACT_NONE}, out{c.out_w, c.out_b, Hc, Hc, EPI_RESADD_F32, ACT_NONE},
+                         fc1{c.fc1_w, c.fc1_b, Mc, Hc, EPI_OUT_OP, ACT_QUICK_GELU}, fc2{c.fc2_w, c.fc2_b, Hc, Mc, EPI_RESADD_F32, ACT_NONE};
+            Operand n = norm_rows(h, st, fv, &qkv, h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+            const Operand q = linear(h, st, fv, qkv, n, h->clip_qkv);
             AttnParams ap{h->clip_qkv, h->clip_qkv, h->clip_qkv, h->clip_att, nullptr, nullptr, 0, 3 * Hc, Hc, 0, Hc, 2 * Hc, T, d.clip_heads, 0.125f, 1};
-            apply_prec(h, ap);
-            emulate_attention_lo8(h, ap, Rc, d.clip_heads, 64, st);
+            Operand att = apply_prec(h, fv, ap, q, Rc);
+            emulate_attention_lo8(h, fv, ap, Rc, d.clip_heads, 64, st);
             launch_attention(ap, NC, 64, false, h->op_dt, st);
-            gemm(h, st, h->clip_att, c.out_w, h->clip_x, c.out_b, Rc, Hc, Hc, Hc, Hc, Hc, EPI_RESADD_F32, ACT_NONE);
-            launch_norm_rows(h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps, h->op_dt, st, h->prec, 1,
-                             lo8_norm_target(h, GemmParams{h->clip_h, c.fc1_w, h->clip_ff, c.fc1_b, Rc, Mc, Hc, Hc, Hc, Mc, EPI_OUT_OP, ACT_QUICK_GELU, nullptr, 0, 0}));
-            gemm(h, st, h->clip_h, c.fc1_w, h->clip_ff, c.fc1_b, Rc, Mc, Hc, Hc, Hc, Mc, EPI_OUT_OP, ACT_QUICK_GELU, nullptr, c.fc2_w, Hc);
-            gemm(h, st, h->clip_ff, c.fc2_w, h->clip_x, c.fc2_b, Rc, Hc, Mc, Mc, Mc, Hc, EPI_RESADD_F32, ACT_NONE);
+            linear(h, st, fv, out, att, h->clip_x);
+            n = norm_rows(h, st, fv, &fc1, h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+            Operand ff = linear(h, st, fv, fc1, n, h->clip_ff, &fc2);
+            linear(h, st, fv, fc2, ff, h->clip_x);
         }
+        const Linear p0{h->p0_w, h->p0_b, D, h->llava ? Hc : 4 * Hc, EPI_OUT_OP, ACT_GELU_ERF}, p2{h->p2_w, h->p2_b, D, D, EPI_OUT_F32, ACT_NONE};
         if (h->llava) {
             // ---- per-token projector, then anyres packing (modeling_llava_next.py get_image_features/pack_image_features) ----
-            launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, h->prec);
-            gemm(h, st, h->hdA, h->p0_w, h->proj1, h->p0_b, Rp, D, Hc, Hc, Hc, D, EPI_OUT_OP, ACT_GELU_ERF, nullptr, h->p2_w, D);
-            gemm(h, st, h->proj1, h->p2_w, h->pf32, h->p2_b, Rp, D, D, D, D, D, EPI_OUT_F32, ACT_NONE);
+            launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, fv.prec);
+            Operand a = operand16(h->hdA, Hc, Rp, fv);
+            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+            linear(h, st, fv, p2, p1, h->pf32);
             launch_llava_pack(h->pf32, d_lsmp, B, SV, h->G, D, h->newline, h->ev, st);
         } else {
             // ---- HD transform + projector (modeling_phi3_v.py:254-303) ----
-            launch_hd_gather(h->clip_x, d_smp, B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, h->prec);
-            gemm(h, st, h->hdA, h->p0_w, h->proj1, h->p0_b, SV, D, 4 * Hc, 4 * Hc, 4 * Hc, D, EPI_OUT_OP, ACT_GELU_ERF, nullptr, h->p2_w, D);
-            gemm(h, st, h->proj1, h->p2_w, h->ev, h->p2_b, SV, D, D, D, D, D, EPI_OUT_F32, ACT_NONE);
+            launch_hd_gather(h->clip_x, d_smp, B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, fv.prec);
+            Operand a = operand16(h->hdA, 4 * Hc, SV, fv);
+            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+            linear(h, st, fv, p2, p1, h->ev);
         }
-        h->set_form(-1);          // (the vision stage's operand form, lr_set_precision_map, covers the projector)
         // ---- embeddings, positions (modeling_phi3_v.py:228-249, rw_model:344-345 | llava: masked_scatter, arange positions) ----
         const int Rl = B * S;
         launch_token_plan(input_ids, attention_mask, B, S, d_voff, h->img_row, h->pos_ids, h->tstat, st,

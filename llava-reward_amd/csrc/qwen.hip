@@ -179,7 +179,7 @@ void finalize_qwen(lr_engine* h) {
     const size_t B = d.max_batch, S = d.max_seq, P = d.max_patches, D = d.hidden, I = d.intermediate;
     const size_t PAD = 256, Rv = P + PAD, Rm = P / h->vunit + PAD, Rl = B * S + PAD;
     auto W = [&](size_t bytes) { return h->dalloc(bytes, false); };
-    const size_t ob = 2 * (size_t)(1 + h->prec);      // bytes per operand element (hi [+ lo])
+    const size_t ob = 2 * (size_t)(1 + h->created.prec);      // bytes per operand element (hi [+ lo])
     h->vA = W(Rv * h->vKpad * ob); h->vx = (float*)W(Rv * h->vH * 4); h->vhn = W(Rv * h->vH * ob);
     h->vqkv = W(Rv * 3 * h->vHp * ob); h->vatt = W(Rv * h->vHp * ob);
     h->vff = W(Rv * h->vIp * ob); h->vcs = (float*)W(Rv * h->vhdp * 4); h->vm1 = W(Rm * h->vHm * ob);
@@ -321,46 +321,38 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         h->lastB = B; h->lastS = S; h->lastP = N; h->lastSV = M;
 
         // ---- ViT (Qwen2_5_VisionTransformerPretrainedModel.forward), window order throughout ----
-        h->set_form(h->pm_clip);          // lr_set_precision_map: the vision tower's operand form
-        launch_qwen_patch_gather(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_src, N, h->vK, h->vKpad, h->vA, h->op_dt, st, h->prec);
-        gemm(h, st, h->vA, h->vpatch_w, h->vx, nullptr, N, vH, h->vKpad, h->vKpad, h->vKpad, vH, EPI_OUT_F32, ACT_NONE);
+        const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision tower's operand form
+        launch_qwen_patch_gather(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_src, N, h->vK, h->vKpad, h->vA, h->op_dt, st, fv.prec);
+        Operand pa = operand16(h->vA, h->vKpad, N, fv);
+        linear(h, st, fv, Linear{h->vpatch_w, nullptr, vH, h->vKpad, EPI_OUT_F32, ACT_NONE}, pa, h->vx);
         launch_vit_rope_table(d_hw, N, h->vinv, h->vhd / 4, vhdp / 2, h->vcs, st);
         const int nvl = h->lim_clip >= 0 && h->lim_clip < d.vit_depth ? h->lim_clip : d.vit_depth;
         const float vscale = 1.0f / std::sqrt((float)h->vhd);
+        // (the ViT and merger norms name no reader: they write 16-bit residuals and the GEMM re-encodes them in place)
         for (int l = 0; l < nvl; ++l) {
             const VitLayer& L = h->vl[l];
             bool full = false;
             for (int i = 0; i < d.vit_n_fullatt; ++i) full = full || d.vit_fullatt[i] == l;
-            launch_norm_rows(h->vx, L.n1, nullptr, h->vhn, N, vH, d.vit_eps, h->op_dt, st, h->prec);
-            {
-                GemmParams gp{h->vhn, L.qkv_w, h->vqkv, L.qkv_b, N, 3 * vHp, vH, vH, vH, 3 * vHp, EPI_ROPE_OP, ACT_NONE, h->vcs, 2 * vHp, vhdp};
-                apply_prec_base(h, gp);
-                if ((2 * vHp) % 256 == 0 && w8a8_eligible(h, gp)) {
-                    launch_w8a8(h, gp, st);
-                } else if ((2 * vHp) % 256 == 0 && (lo8_eligible(h, gp) || gemm_bt_is_deep(gp, h->gemm_tile))) {
-                    upgrade_lo8(h, gp, st);
-                    launch_gemm_bt(gp, h->op_dt, h->gemm_tile, st);
-                } else {
-                    if (!h->vqkv32) h->vqkv32 = (float*)h->dalloc(((size_t)d.max_patches + 256) * 3 * vHp * 4, false);      // fallback only
-                    gemm(h, st, h->vhn, L.qkv_w, h->vqkv32, L.qkv_b, N, 3 * vHp, vH, vH, vH, 3 * vHp, EPI_OUT_F32, ACT_NONE);
-                    launch_rope_split(h->vqkv32, h->vcs, h->vqkv, N, 2 * vHp, vHp, vhdp, h->op_dt, st, h->prec);
-                }
-            }
+            const Linear qkv{L.qkv_w, L.qkv_b, 3 * vHp, vH, EPI_ROPE_OP, ACT_NONE, nullptr, h->vcs, 2 * vHp, vhdp},
+                         proj{L.proj_w, L.proj_b, vH, vHp, EPI_RESADD_F32, ACT_NONE}, gu{L.gu_w, L.gu_b, 2 * vIp, vH, EPI_SWIGLU_OP, ACT_NONE},
+                         down{L.down_w, L.down_b, vH, vIp, EPI_RESADD_F32, ACT_NONE};
+            Operand n = norm_rows(h, st, fv, nullptr, h->vx, L.n1, nullptr, h->vhn, N, vH, d.vit_eps);
+            const Operand q = qkv_rope(h, st, fv, qkv, n, h->vqkv, h->vqkv32, (size_t)d.max_patches);
             AttnParams ap{h->vqkv, h->vqkv, h->vqkv, h->vatt, nullptr, nullptr, 0, 3 * vHp, vHp, 0, vHp, 2 * vHp, max_seg, d.vit_heads,
                           vscale, 1, full ? d_items_full : d_items_win, full ? nfull : nwin};
-            apply_prec(h, ap);
+            Operand att = apply_prec(h, fv, ap, q, N);
             launch_attention(ap, 1, vhdp, false, h->op_dt, st);
-            gemm(h, st, h->vatt, L.proj_w, h->vx, L.proj_b, N, vH, vHp, vHp, vHp, vH, EPI_RESADD_F32, ACT_NONE);
-            launch_norm_rows(h->vx, L.n2, nullptr, h->vhn, N, vH, d.vit_eps, h->op_dt, st, h->prec);
-            gemm(h, st, h->vhn, L.gu_w, h->vff, L.gu_b, N, 2 * vIp, vH, vH, vH, vIp, EPI_SWIGLU_OP, ACT_NONE, nullptr, L.down_w, vH);
-            gemm(h, st, h->vff, L.down_w, h->vx, L.down_b, N, vH, vIp, vIp, vIp, vH, EPI_RESADD_F32, ACT_NONE);
+            linear(h, st, fv, proj, att, h->vx);
+            n = norm_rows(h, st, fv, nullptr, h->vx, L.n2, nullptr, h->vhn, N, vH, d.vit_eps);
+            Operand ff = linear(h, st, fv, gu, n, h->vff, &down);
+            linear(h, st, fv, down, ff, h->vx);
         }
         // ---- merger (Qwen2_5_VLPatchMerger): RMSNorm, 4 consecutive rows = one LLM token, Linear-GELU-Linear ----
-        launch_norm_rows(h->vx, h->vlnq, nullptr, h->vhn, N, vH, 1e-6f, h->op_dt, st, h->prec, unit);     // rows of one merged token side by side
-        gemm(h, st, h->vhn, h->m0_w, h->vm1, h->m0_b, M, vHm, vHm, vHm, vHm, vHm, EPI_OUT_OP, ACT_GELU_ERF, nullptr, h->m2_w, D);
-        gemm(h, st, h->vm1, h->m2_w, h->ev, h->m2_b, M, D, vHm, vHm, vHm, D, EPI_OUT_F32, ACT_NONE);
+        const Linear m0{h->m0_w, h->m0_b, vHm, vHm, EPI_OUT_OP, ACT_GELU_ERF}, m2{h->m2_w, h->m2_b, D, vHm, EPI_OUT_F32, ACT_NONE};
+        Operand mn = norm_rows(h, st, fv, nullptr, h->vx, h->vlnq, nullptr, h->vhn, N, vH, 1e-6f, unit);     // rows of one merged token side by side
+        Operand m1 = linear(h, st, fv, m0, mn, h->vm1, &m2);
+        linear(h, st, fv, m2, m1, h->ev);
 
-        h->set_form(-1);
         // ---- embeddings + 3-D positions (Qwen2_5_VLModel.forward: masked_scatter, get_rope_index) ----
         const int Rl = B * S;
         // token_plan fills tstat (last / first valid index); its slot ranks are superseded by qwen_plan, so the offsets are don't-cares

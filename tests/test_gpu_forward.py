@@ -242,6 +242,16 @@ def test_precision_sites_are_independent_and_consistent():
         _model(cfg, seed, "f16x2", upload=False).engine.set_precision_sites(2, 1, 1, 1, 1)
     eng.set_precision_sites()
     assert torch.equal(fwd((1, 1, 0, 0)), strict)
+    # a split-operand site on a single-pass layer range: its neighbour would read [hi | lo] rows single-pass (at half their stride).
+    # Every operand carries its layout, so the forward refuses it; resetting the sites clears it.
+    single = fwd((1, 0, 0, 0))
+    eng.set_precision_map(1, 0, 0, 0)
+    eng.set_precision_sites(1, -1, -1, -1, -1)
+    with pytest.raises(HipError):
+        _fwd(m, batch)
+    eng.set_precision_sites()
+    assert torch.equal(_fwd(m, batch), single)
+    assert torch.equal(fwd((1, 1, 0, 0)), strict)
 
 
 def test_probe_rows_do_not_depend_on_the_engine_capacity():
