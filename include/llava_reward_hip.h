@@ -173,6 +173,37 @@ int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int64_t* attent
                     int pix_dtype, const int64_t* image_grid_thw_host, int n_images, int B, int S, int flags,
                     float* rewards_out, void* hip_stream);
 
+/* ---- shared image prefix (Phi-3.5-V handles; exports added under ABI 10) ----
+ * Scoring N captions of ONE image: every prompt is `<|user|>\n<|image_1|>\n{caption}`, so the rows share their first n_prefix tokens,
+ * the image among them.  lr_prefix_build runs the tower, the projector and the decoder once over the first n_shared = n_prefix / 64 * 64
+ * of them and keeps, per decoder layer, their post-RoPE key / value rows (in the operand form of that layer's attention site) plus the
+ * projected image rows; lr_forward_prefixed then scores rows that hold only what follows: [the n_prefix - n_shared (< 64) last prefix
+ * tokens | caption | right padding].  Rewards are bit-identical to lr_forward on the full right-padded rows [B, n_shared + T] with the
+ * image repeated per row.  Caller-owned device memory, everything on the caller's stream, no host synchronisation. */
+typedef struct lr_prefix_info {
+    int32_t struct_size;
+    int32_t n_prefix, n_shared, n_image_tokens;
+    int32_t long_factors;      /* 1 = built with the long su-RoPE factor set (total_len [+ 1] > orig_max_pos) */
+    int32_t n_layers;          /* decoder layers the cache holds (lr_set_layer_limits at build time) */
+    uint64_t weights_epoch;    /* lr_weights_epoch at build time */
+    uint64_t form_signature;   /* precision map, sites, layer limits, kernel settings at build time */
+    uint64_t cache_bytes;
+} lr_prefix_info;
+/* Bytes of a cache for n_shared shared positions and n_image_tokens image rows at the handle's CURRENT operand forms and layer limits. */
+size_t lr_prefix_bytes(lr_handle h, int n_shared, int n_image_tokens);
+/* prefix_ids: device int64 [n_prefix] (image slots negative); pixel_values [1, n_crops, 3, img, img]; image_size: HOST int64 [2];
+ * total_len: the width n_shared + T of the batches the cache will serve (it selects the su-RoPE factor set exactly as lr_forward's S
+ * does; 0 = n_prefix); cache: 256-byte aligned device memory of at least lr_prefix_bytes.  Fills *info (host). */
+int lr_prefix_build(lr_handle h, const int64_t* prefix_ids, int n_prefix, const void* pixel_values, int pix_dtype,
+                    const int64_t* image_size_host, int n_crops, int total_len, void* cache, size_t cache_bytes, lr_prefix_info* info,
+                    void* hip_stream);
+/* input_ids / attention_mask: device int64 [B, T], rows RIGHT-padded, holding everything behind the first n_shared tokens.  flags:
+ * LR_FWD_TRAINING_LAST_TOKEN, LR_FWD_NO_FINAL_NORM.  Refused with the reason in lr_last_error: a cache built before the weights
+ * (lr_weights_epoch) or the operand forms / layer limits changed; a width whose su-RoPE factor set is not the cache's; n_shared + T >
+ * max_seq, B > max_batch; mean_hidden_state, W8A8, LLaVA and Qwen handles; LR_FWD_KEEP_HIDDEN_STATES. */
+int lr_forward_prefixed(lr_handle h, const void* cache, const lr_prefix_info* info, const int64_t* input_ids, const int64_t* attention_mask,
+                        int B, int T, int flags, float* rewards_out, void* hip_stream);
+
 /* `outputs["last_hidden_state"]` of the last forward on this handle (rw_model_general_preference.py:347-353, returned by
  * custom_forward(return_output=True) and read by the trainer's evaluate, rm_trainer_general_preference.py:414-418): the final
  * RMSNorm of every token's residual stream (or the stream itself with no_final_norm, i.e. hidden_states[layer_id]), fp32
@@ -254,6 +285,14 @@ int lr_op_attention_split_ex(const void* Q, const void* K, const void* V, void* 
                              int ldo, int qoff, int koff, int voff, int lo_off, int o_split, int batch, int S, int heads,
                              int head_dim, int causal, int kv_group, float scale, float lazy_threshold, int operand_dtype,
                              void* hip_stream);
+/* Shared-key-prefix form (causal, batched; head_dim 96 or 128): the keys of sequence b are [n_shared rows of ONE image Ks / Vs that every
+ * sequence reads | its own S rows of K / V]; Q, mask [batch, S] and O [batch * S rows] describe the own rows, own row i sits at position
+ * n_shared + i; shared keys are always visible.  Ks / Vs rows are laid out like K / V rows (ldq, koff / voff, lo_off); n_shared is a
+ * positive multiple of 64.  lo_off == 0: single operands (lazy_threshold ignored).  Outputs are bit-identical to the own rows of
+ * lr_op_attention / lr_op_attention_split_ex on sequences of n_shared + S rows that all start with the shared rows. */
+int lr_op_attention_shared(const void* Q, const void* K, const void* V, const void* Ks, const void* Vs, void* O, const int64_t* mask,
+                           int n_shared, int ldq, int ldo, int qoff, int koff, int voff, int lo_off, int o_split, int batch, int S, int heads,
+                           int head_dim, int kv_group, float scale, float lazy_threshold, int operand_dtype, void* hip_stream);
 /* Block-diagonal (ragged) dense attention: rows [cu[i], cu[i+1]) attend to each other only (the ViT's windows /
  * images, transformers Qwen2_5_VLVisionAttention over cu_seqlens).  cu_seqlens: HOST int32 [n_seg + 1]. */
 int lr_op_attention_segments(const void* Q, const void* K, const void* V, void* O, const int32_t* cu_seqlens_host, int n_seg,

@@ -71,7 +71,13 @@ constexpr int ATT_MAX_S = 8192;        // keys covered by the LDS bitmask
 // NW = waves per workgroup: 4 (128 queries; two workgroups share a CU when LDS allows) or 8 (256 queries on one K/V ring: used
 // by the split-operand mode, whose ring fills the LDS, so that every SIMD still holds two waves; waves 4-7 issue no DMA).
 // PP = ping-pong schedule of an 8-wave workgroup (long sequences; see the comment at the loop).
-template <typename OT, int HD, bool CAUSAL, bool PREC, int NW, bool PP = false>
+// SH = shared-key-prefix form (AttnParams::n_shared; causal, batched): the keys of every sequence are [n_shared rows
+// of ONE K/V image that all sequences read | the sequence's own p.S rows]; queries, mask and O exist for the own rows only, own row i
+// sits at position n_shared + i.  Everything below works on those absolute positions: the query tiles are the ones the full launch at
+// S = n_shared + p.S would cut (end-aligned shift included), of which only those that hold an own row are launched; positions below
+// n_shared inside a launched tile are dead lanes (Q loads clamped, nothing stored).  The instantiations live in attention_shared.hip;
+// with SH false every line of it folds away.
+template <typename OT, int HD, bool CAUSAL, bool PREC, int NW, bool PP = false, bool SH = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnParams p) {   // <= 256 unified registers per wave, MFMA results stay in VGPRs
     constexpr int KT = 64;                 // keys per tile
     constexpr int KSTEPS = HD / 16;        // MFMA k-steps over the head dim
@@ -107,15 +113,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
     }
     int S = p.S, qt, qsel = -1, qshift = 0;
     size_t rowbase;
+    const int NSH = SH ? p.n_shared : 0;           // shared keys in front of the own rows (a multiple of the key tile)
     if (!CAUSAL && p.items) {                      // ragged mode: one segment per workgroup
         const int4 it = p.items[bx];
         rowbase = (size_t)it.x; S = it.y; qt = it.z;
     } else if (CAUSAL && p.qsel) {                 // gathered mode: the query tile that holds the wanted query of sequence b
         qsel = __builtin_amdgcn_readfirstlane(p.qsel_last ? S - 1 : min(max(p.qsel[b * p.qsel_stride], 0), S - 1));
+        if constexpr (SH) qsel += NSH;
         qt = qsel / (NW * 32);
         rowbase = (size_t)b * S;
     } else {
-        const int nqt = (S + NW * 32 - 1) / (NW * 32);
+        const int nqt = (S + NSH + NW * 32 - 1) / (NW * 32);
         qt = nqt - 1 - bx;                         // heavy (late) causal tiles first
         rowbase = (size_t)b * S;
         // Causal: the query tiles are shifted towards the END of the sequence (by whole key tiles, so that a wave's diagonal stays
@@ -127,20 +135,23 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
         // Ping-pong kernels only (S >= 1024: one workgroup per CU, lock-stepped tile periods: -10 % at S = 2642 together with the
         // XCD-aware order, tools/dbg/attn_equal.py); the shorter-sequence forms, whose waves are not lock-stepped in pairs, measured
         // level to worse with it (S = 800 .. 960: +1 .. +9 %) and keep the front-aligned tiles.
-        if (CAUSAL && PP && p.q_end_aligned) qshift = (nqt * (NW * 32) - S) / KT * KT;
+        if (CAUSAL && PP && p.q_end_aligned) qshift = (nqt * (NW * 32) - (S + NSH)) / KT * KT;
     }
+    const int St = S + NSH;                        // keys of a sequence = positions the tiling covers (ragged mode: S is the segment's by now)
     const int q0 = qt * (NW * 32) - qshift + wave * 32;
 
     const unsigned short* Qp = (const unsigned short*)p.Q + p.qoff + head * HD;
     const int kvh = head / p.kv_group;                 // GQA: several query heads share one key/value head
     const unsigned short* Kp = (const unsigned short*)p.K + p.koff + kvh * HD;
     const unsigned short* Vp = (const unsigned short*)p.V + p.voff + kvh * HD;
+    const unsigned short* Ksp = SH ? (const unsigned short*)p.Ks + p.koff + kvh * HD : nullptr;      // the shared image: rows laid out like K / V
+    const unsigned short* Vsp = SH ? (const unsigned short*)p.Vs + p.voff + kvh * HD : nullptr;
 
     // ---- key range of this workgroup ----
-    int kbeg = 0, kend = S;
+    int kbeg = 0, kend = St;
     if (CAUSAL) {
-        kend = min(S, qt * (NW * 32) - qshift + NW * 32);
-        if (p.kmin) kbeg = (min(p.kmin[b * p.kmin_stride], S) / KT) * KT;
+        kend = min(St, qt * (NW * 32) - qshift + NW * 32);
+        if (!SH && p.kmin) kbeg = (min(p.kmin[b * p.kmin_stride], S) / KT) * KT;
     }
     const int ntiles = kbeg < kend ? (kend - kbeg + KT - 1) / KT : 0;
 
@@ -192,9 +203,18 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
         const int slot = t % NSLOT;
         const int k0 = kbeg + t * KT;
         const unsigned dstK = __builtin_amdgcn_readfirstlane(lds_base + slot * NOPS * TILE + (wave & 3) * 1024);
-        const unsigned short* bK = uni(Kp + (rowbase + k0) * p.ldq);
-        const unsigned short* bV = uni(Vp + (rowbase + k0) * p.ldq);
-        if (k0 + KT <= S) {
+        // SH: a uniform choice of the scalar base per tile -- below n_shared the shared image, else the sequence's rows at key k0 - n_shared
+        const bool shared_tile = SH && k0 < NSH;
+        const int kl = (SH && !shared_tile) ? k0 - NSH : k0;          // first key of the tile as a row of its source
+        const unsigned short *bK, *bV;
+        if constexpr (SH) {
+            bK = uni((shared_tile ? Ksp : Kp + rowbase * p.ldq) + (size_t)kl * p.ldq);
+            bV = uni((shared_tile ? Vsp : Vp + rowbase * p.ldq) + (size_t)kl * p.ldq);
+        } else {
+            bK = uni(Kp + (rowbase + k0) * p.ldq);
+            bV = uni(Vp + (rowbase + k0) * p.ldq);
+        }
+        if (shared_tile || kl + KT <= S) {
 #pragma unroll
             for (int it = 0; it < NPO; ++it) {
                 const unsigned dk = dstK + it * 4096;
@@ -209,7 +229,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
 #pragma unroll
             for (int it = 0; it < NPO; ++it) {
                 const int r = (it * 256 + (tid & 255)) / CH;
-                const unsigned back = (unsigned)(max(k0 + r - (S - 1), 0) * p.ldq) * 2u;
+                const unsigned back = (unsigned)(max(kl + r - (S - 1), 0) * p.ldq) * 2u;
                 const unsigned dk = dstK + it * 4096;
                 if (doK) dma(bK, offK[it] - back, dk);
                 if (doV) dma(bV, offV[it] - back, dk + TILE);
@@ -228,14 +248,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
     //  for ten key tiles or fewer.)
     uint4 qf[KSTEPS];       // lane (c,h) holds Q[q0+c][16*ks + 8h .. +7]
     {
-        const int qrow = max(min(q0 + lc, S - 1), 0);
+        const int qrow = max(min(q0 + lc - NSH, S - 1), 0);
         const unsigned short* src = Qp + (rowbase + qrow) * p.ldq + 8 * lh;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) qf[ks] = *(const uint4*)(src + 16 * ks);
     }
     uint4 qfl[PREC ? KSTEPS : 1];       // residuals of the same Q elements
     if constexpr (PREC) {
-        const int qrow = max(min(q0 + lc, S - 1), 0);
+        const int qrow = max(min(q0 + lc - NSH, S - 1), 0);
         const unsigned short* src = Qp + (rowbase + qrow) * p.ldq + p.lo_off + 8 * lh;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ++ks) qfl[ks] = *(const uint4*)(src + 16 * ks);
@@ -254,17 +274,21 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
             for (int w = w0 + wave; w < w1; w += NW * J) {
                 int64_t mv[J];
 #pragma unroll
-                for (int j = 0; j < J; ++j) mv[j] = mrow[min(min(w + j * NW, w1 - 1) * KT + lane, S - 1)];
+                for (int j = 0; j < J; ++j) {
+                    int mi = min(min(w + j * NW, w1 - 1) * KT + lane, St - 1) - NSH;       // (the mask covers the own rows)
+                    if constexpr (SH) mi = max(mi, 0);
+                    mv[j] = mrow[mi];
+                }
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     const int ww = w + j * NW;
-                    const unsigned long long bits = __ballot(ww * KT + lane < S && mv[j] != 0);
+                    const unsigned long long bits = __ballot(ww * KT + lane < St && ((SH && ww * KT < NSH) || mv[j] != 0));     // shared keys: always visible
                     if (ww < w1 && lane == 0) { sBits[2 * ww] = (unsigned)bits; sBits[2 * ww + 1] = (unsigned)(bits >> 32); }
                 }
             }
         } else {
             for (int w = w0 + wave; w < w1; w += NW) {
-                const unsigned long long bits = __ballot(w * KT + lane < S);
+                const unsigned long long bits = __ballot(w * KT + lane < St);
                 if (lane == 0) { sBits[2 * w] = (unsigned)bits; sBits[2 * w + 1] = (unsigned)(bits >> 32); }
             }
         }
@@ -546,8 +570,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
         // Two loops instead of `if (act(t))` around every segment: with the conditions inside one loop S and P were both loop-carried
         // (each keeps its old value on the untaken path), 64 registers where 32 are live -- the registers the fragment ring needs.
         int nact = 0;
-        if (q0 < S && ntiles > 0) nact = CAUSAL ? max(0, min(ntiles, (q0 + 31 - kbeg) / KT + 1)) : ntiles;
+        if (q0 < St && ntiles > 0) nact = CAUSAL ? max(0, min(ntiles, (q0 + 31 - kbeg) / KT + 1)) : ntiles;
         if (CAUSAL && q0 + 31 < kbeg) nact = 0;
+        if (SH && q0 + 31 < NSH) nact = 0;                // a wave that holds no own row: the DMA stream and the barriers only
         nact = __builtin_amdgcn_readfirstlane(nact);
         auto vec_dma = [&](int t) {
 #if !(defined(LR_ATT_DIAG) && (LR_ATT_DIAG & 8))          // diagnostic 8: no DMA in the loop (tiles 0, 1 only), results invalid
@@ -627,7 +652,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
         // all lie beyond the sequence (577 tokens = 4.5 x 128 queries: the last workgroup's fourth wave).
         // (Skipping the 32-key score halves / 16-key PV steps of a last key tile that holds no key -- 577 = 9 x 64 + 1 -- was built
         //  and measured level: the branches cost what the skipped MFMAs save.)
-        const bool active = (!CAUSAL || (k0 <= q0 + 31)) && q0 < S;
+        const bool active = (!CAUSAL || (k0 <= q0 + 31)) && q0 < St && (!SH || q0 + 31 >= NSH);
         if (active) {
             qk(t);            // S^T tiles: keys kt*32 + [(r&3) + 8(r>>2) + 4h], query lc
             soft(t);          // masks where the tile needs them, online softmax in log2 units, P -> operand type (chunk 0)
@@ -639,9 +664,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
     }
 
     // ---- epilogue: O[q][d], d = dt*32 + (r&3) + 8(r>>2) + 4h : 4 consecutive d per register quad ----
-    if (qsel >= 0 ? qpos == qsel : (qpos < S && qpos >= 0)) {
+    if (qsel >= 0 ? qpos == qsel : (qpos < St && qpos >= NSH)) {
         const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-        unsigned short* dst = (unsigned short*)p.O + (qsel >= 0 ? (size_t)b : rowbase + qpos) * p.ldo + head * HD + 4 * lh;
+        unsigned short* dst = (unsigned short*)p.O + (qsel >= 0 ? (size_t)b : rowbase + qpos - NSH) * p.ldo + head * HD + 4 * lh;
 #pragma unroll
         for (int d = 0; d < DT; ++d)
 #pragma unroll
@@ -655,6 +680,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_kernel(AttnPara
     }
 }
 
+#ifndef LR_ATT_SHARED_TU
 template <typename OT, int HD, bool CAUSAL>
 static void launch_one(const AttnParams& p0, int batch, hipStream_t st) {
     AttnParams p = p0;
@@ -721,5 +747,68 @@ void launch_attention(const AttnParams& p, int batch, int head_dim, bool causal,
     else if (head_dim == 128 && causal) { f16 ? launch_one<F16, 128, true>(p, batch, st) : launch_one<BF16, 128, true>(p, batch, st); }
     else throw std::runtime_error("attention: head_dim must be 64, 96 or 128 (128: causal only)");
 }
+#else   // LR_ATT_SHARED_TU: the shared-key-prefix instantiations and their launcher (attention_shared.hip)
+// The instantiation is chosen on the TOTAL key count n_shared + S, exactly as launch_one chooses for a full launch of that length, and
+// the grid holds the query tiles of that full launch that reach past n_shared.
+template <typename OT, int HD>
+static void launch_shared_one(const AttnParams& p0, int batch, hipStream_t st) {
+    AttnParams p = p0;
+    const int St = p.S + p.n_shared;
+    const char* xe = getenv("LR_ATT_XCD_ORDER");
+    const bool xcd_order = !xe || atoi(xe) != 0;
+    const char* qe = getenv("LR_ATT_QSHIFT");
+    p.q_end_aligned = (!qe || atoi(qe) != 0) ? 1 : 0;
+    const char* pe = getenv("LR_ATT_PINGPONG");
+    const bool pingpong = !pe || atoi(pe) != 0;
+    const char* pm = getenv("LR_ATT_PP_MIN_S");
+    const int pp_min = pm ? atoi(pm) : 1024;
+    auto own_tiles = [&](int nq, bool pp) {            // nq queries per workgroup: tile qt covers positions [qt nq - shift, + nq)
+        if (p.qsel) return 1;
+        const int nqt = (St + nq - 1) / nq;
+        const int shift = (pp && p.q_end_aligned) ? (nqt * nq - St) / 64 * 64 : 0;
+        return nqt - (p.n_shared + shift) / nq;
+    };
+    auto grid = [&](int nq) {
+        if (!xcd_order) { p.lin_nqt = 0; p.lin_batch = 0; return dim3(nq, p.heads, batch); }
+        p.lin_nqt = nq; p.lin_batch = batch;
+        const int kvpairs = p.heads / p.kv_group * batch;
+        return dim3((unsigned)((kvpairs + 7) / 8 * 8 * p.kv_group * nq), 1, 1);
+    };
+    if (p.lo_off == 0 && St >= pp_min && pingpong) {
+        const dim3 g = grid(own_tiles(256, true));
+        hipLaunchKernelGGL((attn_kernel<OT, HD, true, false, 8, true, true>), g, dim3(512), 0, st, p);
+    } else if (p.lo_off > 0 && St >= pp_min && HD != 128 && pingpong) {
+        if constexpr (HD != 128) {
+            const dim3 g = grid(own_tiles(256, true));
+            hipLaunchKernelGGL((attn_kernel<OT, HD, true, true, 8, true, true>), g, dim3(512), 0, st, p);
+        }
+    } else if (p.lo_off > 0 && St > 128) {
+        const dim3 g = grid(own_tiles(256, false));
+        hipLaunchKernelGGL((attn_kernel<OT, HD, true, true, 8, false, true>), g, dim3(512), 0, st, p);
+    } else if (p.lo_off > 0) {
+        const dim3 g = grid(own_tiles(128, false));
+        hipLaunchKernelGGL((attn_kernel<OT, HD, true, true, 4, false, true>), g, dim3(256), 0, st, p);
+    } else {
+        const dim3 g = grid(own_tiles(128, false));
+        hipLaunchKernelGGL((attn_kernel<OT, HD, true, false, 4, false, true>), g, dim3(256), 0, st, p);
+    }
+}
+
+void launch_attention_shared(const AttnParams& p, int batch, int head_dim, int operand_dtype, hipStream_t st) {
+    if (batch <= 0) return;
+    if (p.ldq % 8 || p.qoff % 8 || p.koff % 8 || p.voff % 8 || p.ldo % 4)
+        throw std::runtime_error("attention: operand rows must be 16-byte aligned");
+    if (p.lo_off < 0 || p.lo_off % 8 || p.o_split < 0 || p.o_split % 4) throw std::runtime_error("attention: bad split-operand offsets");
+    if (p.n_shared <= 0 || p.n_shared % 64 || !p.Ks || !p.Vs) throw std::runtime_error("attention (shared prefix): n_shared must be a positive multiple of the 64-key tile, with a shared K / V image");
+    if (p.items || p.kmin) throw std::runtime_error("attention (shared prefix): batched and causal, every shared key visible (no ragged items, no kmin)");
+    if (p.S < 1 || p.S + p.n_shared > ATT_MAX_S) throw std::runtime_error("attention: sequence length above 8192 is not supported");
+    if (p.kv_group < 1 || p.heads % p.kv_group) throw std::runtime_error("attention: heads must be a multiple of kv_group");
+    if (!(p.lazy_t >= 0.f && p.lazy_t <= 15.f)) throw std::runtime_error("attention: lazy_t (reference-maximum threshold, log2 units) must be in [0, 15]");
+    const bool f16 = operand_dtype == DT_F16;
+    if (head_dim == 96) { f16 ? launch_shared_one<F16, 96>(p, batch, st) : launch_shared_one<BF16, 96>(p, batch, st); }
+    else if (head_dim == 128) { f16 ? launch_shared_one<F16, 128>(p, batch, st) : launch_shared_one<BF16, 128>(p, batch, st); }
+    else throw std::runtime_error("attention (shared prefix): head_dim must be 96 or 128");
+}
+#endif  // LR_ATT_SHARED_TU
 
 }  // namespace lr

@@ -290,6 +290,13 @@ struct AttnParams {
     // (log2 units, 0 .. 15).  The engine passes ATT_LAZY_T_DEFAULT in stages that run the e4m3-residual default form and 0 (exact,
     // the reference's own arithmetic) in stages that run the strict form.
     float lazy_t;
+    // shared-key-prefix form (launch_attention_shared only; causal, batched): the keys of every sequence are
+    // [n_shared rows of the image Ks / Vs, which ALL sequences read | the sequence's own S rows of K / V].  Ks / Vs rows are laid out
+    // like K / V rows (ldq, koff / voff, lo_off).  Q, mask, O and S describe the own rows only; own row i sits at position
+    // n_shared + i; shared keys are always visible.  n_shared: a positive multiple of the 64-key tile.  0 / null = off.
+    const void* Ks;
+    const void* Vs;
+    int n_shared;
 };
 constexpr float ATT_LAZY_T_DEFAULT = 8.f;
 

@@ -289,6 +289,180 @@ void run_mean_pool_head(lr_engine* h, hipStream_t st, const int64_t* attention_m
     launch_reward_head(h->hL, nullptr, nullptr, 0.f, h->vh, d.value_head_dim, rewards_out, B, D, st);
 }
 
+// The image side of a pass, shared by lr_forward and lr_prefix_build: host plan (active crops, per-sample vision geometry, image-token
+// offsets) through the table ring, CLIP tower, HD transform / anyres packing and the projector; leaves the image rows in h->ev.
+struct VisionPlan { const int* d_voff; const int* voff; int SV, Vmax; };
+static VisionPlan run_vision(lr_engine* h, hipStream_t st, const void* pixel_values, int pix_dtype, const int64_t* image_sizes_host, int B,
+                             int S, int n_crops, const char* who) {
+        const lr_model_desc& d = h->d;
+        const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, T = h->T, g2 = h->G / 2;
+        const int img = d.clip_image;
+
+        // ---- host plan: active crops, per-sample vision geometry, image-token offsets ----
+        // Phi-3-V: modeling_phi3_v.py:276-297 (HD crop grid);  LLaVA: modeling_llava_next.py:41-146,265-335 (anyres + unpad)
+        const int slot = h->slot_i; h->slot_i = (h->slot_i + 1) % lr_engine::NSLOT;
+        if (h->tab_used[slot]) LR_HIP_CHECK(hipEventSynchronize(h->tab_ev[slot]));   // bounds host run-ahead to NSLOT passes
+        char* th = h->tab_host + (size_t)slot * h->tab_bytes;
+        char* td = h->tab_dev + (size_t)slot * h->tab_bytes;
+        const size_t NCcap = (size_t)d.max_batch * d.max_crops;
+        const size_t smp_off = NCcap * 4, voff_off = smp_off + (size_t)d.max_batch * sizeof(LlavaSample);
+        int* crop_src = (int*)th;
+        HdSample* smp = (HdSample*)(th + smp_off);
+        LlavaSample* lsmp = (LlavaSample*)(th + smp_off);
+        int* voff = (int*)(th + voff_off);
+        int NC = 0, SV = 0, Vmax = 0;
+        for (int b = 0; b < B; ++b) {
+            const int64_t hh = image_sizes_host[2 * b], ww = image_sizes_host[2 * b + 1];
+            int ncr, V;
+            if (h->llava) {
+                if (hh <= 0 || ww <= 0) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive");
+                // transformers select_best_resolution: max effective resolution, then min waste
+                long best_eff = 0, best_waste = 0; int bh = 0, bw = 0;
+                for (int i = 0; i < d.n_pinpoints; ++i) {
+                    const int ph = d.pinpoints[2 * i], pw = d.pinpoints[2 * i + 1];
+                    const double sc = std::min((double)pw / (double)ww, (double)ph / (double)hh);
+                    const long dw = (long)((double)ww * sc), dh = (long)((double)hh * sc);
+                    const long eff = std::min(dw * dh, (long)(ww * hh)), waste = (long)pw * ph - eff;
+                    if (eff > best_eff || (eff == best_eff && (bh == 0 || waste < best_waste))) { best_eff = eff; best_waste = waste; bh = ph; bw = pw; }
+                }
+                const int gh = bh / img, gw = bw / img, ch = gh * h->G, cw = gw * h->G;
+                int r0 = 0, r1 = ch, c0 = 0, c1 = cw;
+                // unpad_image (modeling_llava_next.py:109-146): new extent = int(round(x, 7)) -- 7 decimals, then truncation
+                auto trunc7 = [](double x) { return (int)(std::round(x * 1e7) / 1e7); };
+                if ((double)ww / (double)hh > (double)cw / (double)ch) {           // rows were padded
+                    const int pad = (ch - trunc7((double)hh * ((double)cw / (double)ww))) / 2; r0 = pad; r1 = ch - pad;
+                } else {                                                           // columns were padded
+                    const int pad = (cw - trunc7((double)ww * ((double)ch / (double)hh))) / 2; c0 = pad; c1 = cw - pad;
+                }
+                ncr = 1 + gh * gw;
+                V = h->G * h->G + (r1 - r0) * (c1 - c0 + 1);
+                lsmp[b] = LlavaSample{gh, gw, r0, r1, c0, c1, NC, SV};
+            } else {
+                if (hh <= 0 || ww <= 0 || hh % img || ww % img) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive multiples of the crop size");
+                const int hc = (int)(hh / img), wc = (int)(ww / img);
+                ncr = hc * wc + 1;
+                smp[b] = HdSample{hc, wc, NC, SV};
+                V = hc * g2 * (wc * g2 + 1) + 1 + g2 * (g2 + 1);
+            }
+            if (ncr > n_crops) throw std::invalid_argument(std::string(who) + ": image_sizes needs more crops than pixel_values holds");
+            voff[b] = SV;
+            for (int c = 0; c < ncr; ++c) crop_src[NC++] = b * n_crops + c;
+            SV += V;
+            Vmax = V > Vmax ? V : Vmax;
+        }
+        voff[B] = SV;
+        LR_HIP_CHECK(hipMemcpyAsync(td, th, h->tab_bytes, hipMemcpyHostToDevice, st));
+        LR_HIP_CHECK(hipEventRecord(h->tab_ev[slot], st));
+        h->tab_used[slot] = true;
+        const int* d_crop_src = (const int*)td;
+        const HdSample* d_smp = (const HdSample*)(td + smp_off);
+        const LlavaSample* d_lsmp = (const LlavaSample*)(td + smp_off);
+        const int* d_voff = (const int*)(td + voff_off);
+        h->lastB = B; h->lastS = S; h->lastNC = NC; h->lastSV = SV; h->lastVmax = Vmax;
+        h->last_voff.assign(voff, voff + B + 1);
+
+        // ---- CLIP tower (utils/utils.py:266-273) ----
+        const int Rp = NC * (T - 1), Rc = NC * T;
+        const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision stage's operand form (covers the projector)
+        launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, img, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, fv.prec);
+        Operand pa = operand16(h->patchA, h->Kpad, Rp, fv);
+        linear(h, st, fv, Linear{h->patch_w, nullptr, Hc, h->Kpad, EPI_OUT_F32, ACT_NONE}, pa, h->patch_out);
+        launch_clip_embed(h->patch_out, h->cls, h->pos, h->pre_w, h->pre_b, h->clip_x, NC, T, Hc, d.clip_ln_eps, st);
+        const int ncl = h->lim_clip >= 0 && h->lim_clip < d.clip_layers ? h->lim_clip : d.clip_layers;
+        for (int l = 0; l < ncl; ++l) {
+            const ClipLayer& c = h->cl[l];
+            const Linear qkv{c.qkv_w, c.qkv_b, 3 * Hc, Hc, EPI_OUT_OP, ACT_NONE}, out{c.out_w, c.out_b, Hc, Hc, EPI_RESADD_F32, ACT_NONE},
+                         fc1{c.fc1_w, c.fc1_b, Mc, Hc, EPI_OUT_OP, ACT_QUICK_GELU}, fc2{c.fc2_w, c.fc2_b, Hc, Mc, EPI_RESADD_F32, ACT_NONE};
+            Operand n = norm_rows(h, st, fv, &qkv, h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+            const Operand q = linear(h, st, fv, qkv, n, h->clip_qkv);
+            AttnParams ap{h->clip_qkv, h->clip_qkv, h->clip_qkv, h->clip_att, nullptr, nullptr, 0, 3 * Hc, Hc, 0, Hc, 2 * Hc, T, d.clip_heads, 0.125f, 1};
+            Operand att = apply_prec(h, fv, ap, q, Rc);
+            emulate_attention_lo8(h, fv, ap, Rc, d.clip_heads, 64, st);
+            launch_attention(ap, NC, 64, false, h->op_dt, st);
+            linear(h, st, fv, out, att, h->clip_x);
+            n = norm_rows(h, st, fv, &fc1, h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+            Operand ff = linear(h, st, fv, fc1, n, h->clip_ff, &fc2);
+            linear(h, st, fv, fc2, ff, h->clip_x);
+        }
+        const Linear p0{h->p0_w, h->p0_b, D, h->llava ? Hc : 4 * Hc, EPI_OUT_OP, ACT_GELU_ERF}, p2{h->p2_w, h->p2_b, D, D, EPI_OUT_F32, ACT_NONE};
+        if (h->llava) {
+            // ---- per-token projector, then anyres packing (modeling_llava_next.py get_image_features/pack_image_features) ----
+            launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, fv.prec);
+            Operand a = operand16(h->hdA, Hc, Rp, fv);
+            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+            linear(h, st, fv, p2, p1, h->pf32);
+            launch_llava_pack(h->pf32, d_lsmp, B, SV, h->G, D, h->newline, h->ev, st);
+        } else {
+            // ---- HD transform + projector (modeling_phi3_v.py:254-303) ----
+            launch_hd_gather(h->clip_x, d_smp, B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, fv.prec);
+            Operand a = operand16(h->hdA, 4 * Hc, SV, fv);
+            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+            linear(h, st, fv, p2, p1, h->ev);
+        }
+        return VisionPlan{d_voff, voff, SV, Vmax};
+}
+
+// Tail of a pass (rw_model:376-448): final norm of the row each reward is read from, SkipCA over the image rows in `ev`, value head.
+// After a gathered last layer the B rows are already compact in xg (S = 1, position 0).  voff / voff_stride: see launch_token_plan.
+static void reward_tail(lr_engine* h, hipStream_t st, int flags, int S, const float* ev, const int* d_voff, int voff_stride, int Vmax, int B,
+                        float* rewards_out) {
+    const lr_model_desc& d = h->d;
+    const int D = d.hidden;
+    const int last_pos = (flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0;
+    launch_gather_norm_rows(h->last_pruned ? h->xg : h->x, h->tstat, h->last_pruned ? 1 : S, h->last_pruned ? 1 : last_pos,
+                            (flags & LR_FWD_NO_FINAL_NORM) ? nullptr : h->norm_w, d.rms_eps, h->hL, B, D, st);
+    const float* ao = nullptr;
+    if (d.add_cross_attention) {
+        launch_rowvec_linear(h->hL, h->Wq, h->tq, B, D, D, st);
+        launch_rowvec_linear(h->tq, h->WkT, h->tkq, B, D, D, st);
+        launch_ca_scores(ev, h->tkq, d_voff, B, Vmax, D, 1.0f / std::sqrt((float)D), h->tsc, st, voff_stride);
+        launch_ca_softmax(h->tsc, B, Vmax, st);
+        launch_ca_context(ev, h->tsc, d_voff, B, Vmax, D, h->tctx, st, voff_stride);
+        launch_rowvec_linear(h->tctx, h->Wv, h->tao, B, D, D, st);
+        ao = h->tao;
+    }
+    launch_reward_head(h->hL, ao, h->ca_w, d.ca_eps, h->vh, d.value_head_dim, rewards_out, B, D, st);
+    launch_slot_check(h->tstat, d_voff, rewards_out, B, d.value_head_dim, st, voff_stride);
+}
+
+// ---- shared image prefix: layout of a cache and the signature of everything its bits depend on ----
+// [256-byte head: int {0, V, image slots among the shared tokens} | per decoder layer l < nl: the qkv rows of the n_shared shared
+//  positions exactly as that layer's attention site reads them (post-RoPE, [hi | lo] where the site's form is split; the row stride of
+//  the qkv buffer, so the attention kernel's per-thread offsets serve both sources) | ev: V projected image rows, fp32]
+struct PrefixLayout { std::vector<size_t> layer; size_t ev = 0, total = 0; int nl = 0; };
+static PrefixLayout prefix_layout(const lr_engine* h, int n_shared, int V) {
+    PrefixLayout L;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    L.nl = h->lim_layers >= 0 && h->lim_layers < h->d.layers ? h->lim_layers : h->d.layers;
+    size_t off = 256;
+    for (int l = 0; l < L.nl; ++l) {
+        L.layer.push_back(off);
+        off += up((size_t)n_shared * h->Nqkv * 2 * (size_t)(1 + h->site(l, lr_engine::SITE_ATTN).prec));
+    }
+    L.ev = off;
+    L.total = off + up((size_t)V * h->d.hidden * 4);
+    return L;
+}
+static uint64_t prefix_signature(const lr_engine* h) {
+    uint64_t x = 0xCBF29CE484222325ull;
+    auto mix = [&](int64_t v) { x = splitmix64_host(x ^ (uint64_t)v); };
+    mix(h->created.prec); mix(h->created.lo8); mix(h->op_dt); mix(h->w8a8);
+    mix(h->pm_clip); mix(h->pm_mid); mix(h->pm_first); mix(h->pm_last);
+    for (int i = 0; i < lr_engine::N_SITES; ++i) mix(h->pm_site[i]);
+    mix(h->lim_clip); mix(h->lim_layers); mix(h->gemm_tile);
+    mix(__builtin_bit_cast(int, h->att_lazy_t)); mix(__builtin_bit_cast(int, h->att_lazy_t_strict));
+    return x;
+}
+static void prefix_refuse_handle(const lr_engine* h, const char* who) {
+    const std::string w = who;
+    if (!h->finalized) throw std::logic_error(w + ": call lr_finalize first");
+    if (h->qwen) throw std::logic_error(w + ": the shared image prefix serves the Phi-3.5-V backbone; this is a Qwen2.5-VL handle");
+    if (h->llava) throw std::logic_error(w + ": the shared image prefix serves the Phi-3.5-V backbone; this is a LLaVA handle");
+    if (h->d.mean_hidden_state) throw std::logic_error(w + ": mean_hidden_state pools every token of a row, the shared ones included; not served from a prefix cache");
+    if (h->w8a8) throw std::logic_error(w + ": w8a8 handles are not served from a prefix cache");
+    if (h->hd != 96 && h->hd != 128) throw std::logic_error(w + ": the shared-key-prefix attention form exists for head_dim 96 and 128");
+}
+
 extern "C" {
 
 int lr_abi_version(void) { return LR_ABI_VERSION; }
@@ -574,110 +748,9 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
         if (n_crops < 2 || n_crops > d.max_crops) throw std::invalid_argument("lr_forward: n_crops exceeds max_crops");
         if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_forward: pixel dtype must be F32 or BF16");
         hipStream_t st = (hipStream_t)hip_stream;
-        const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, T = h->T, g2 = h->G / 2;
-        const int img = d.clip_image;
-
-        // ---- host plan: active crops, per-sample vision geometry, image-token offsets ----
-        // Phi-3-V: modeling_phi3_v.py:276-297 (HD crop grid);  LLaVA: modeling_llava_next.py:41-146,265-335 (anyres + unpad)
-        const int slot = h->slot_i; h->slot_i = (h->slot_i + 1) % lr_engine::NSLOT;
-        if (h->tab_used[slot]) LR_HIP_CHECK(hipEventSynchronize(h->tab_ev[slot]));   // bounds host run-ahead to NSLOT passes
-        char* th = h->tab_host + (size_t)slot * h->tab_bytes;
-        char* td = h->tab_dev + (size_t)slot * h->tab_bytes;
-        const size_t NCcap = (size_t)d.max_batch * d.max_crops;
-        const size_t smp_off = NCcap * 4, voff_off = smp_off + (size_t)d.max_batch * sizeof(LlavaSample);
-        int* crop_src = (int*)th;
-        HdSample* smp = (HdSample*)(th + smp_off);
-        LlavaSample* lsmp = (LlavaSample*)(th + smp_off);
-        int* voff = (int*)(th + voff_off);
-        int NC = 0, SV = 0, Vmax = 0;
-        for (int b = 0; b < B; ++b) {
-            const int64_t hh = image_sizes_host[2 * b], ww = image_sizes_host[2 * b + 1];
-            int ncr, V;
-            if (h->llava) {
-                if (hh <= 0 || ww <= 0) throw std::invalid_argument("lr_forward: image_sizes must be positive");
-                // transformers select_best_resolution: max effective resolution, then min waste
-                long best_eff = 0, best_waste = 0; int bh = 0, bw = 0;
-                for (int i = 0; i < d.n_pinpoints; ++i) {
-                    const int ph = d.pinpoints[2 * i], pw = d.pinpoints[2 * i + 1];
-                    const double sc = std::min((double)pw / (double)ww, (double)ph / (double)hh);
-                    const long dw = (long)((double)ww * sc), dh = (long)((double)hh * sc);
-                    const long eff = std::min(dw * dh, (long)(ww * hh)), waste = (long)pw * ph - eff;
-                    if (eff > best_eff || (eff == best_eff && (bh == 0 || waste < best_waste))) { best_eff = eff; best_waste = waste; bh = ph; bw = pw; }
-                }
-                const int gh = bh / img, gw = bw / img, ch = gh * h->G, cw = gw * h->G;
-                int r0 = 0, r1 = ch, c0 = 0, c1 = cw;
-                // unpad_image (modeling_llava_next.py:109-146): new extent = int(round(x, 7)) -- 7 decimals, then truncation
-                auto trunc7 = [](double x) { return (int)(std::round(x * 1e7) / 1e7); };
-                if ((double)ww / (double)hh > (double)cw / (double)ch) {           // rows were padded
-                    const int pad = (ch - trunc7((double)hh * ((double)cw / (double)ww))) / 2; r0 = pad; r1 = ch - pad;
-                } else {                                                           // columns were padded
-                    const int pad = (cw - trunc7((double)ww * ((double)ch / (double)hh))) / 2; c0 = pad; c1 = cw - pad;
-                }
-                ncr = 1 + gh * gw;
-                V = h->G * h->G + (r1 - r0) * (c1 - c0 + 1);
-                lsmp[b] = LlavaSample{gh, gw, r0, r1, c0, c1, NC, SV};
-            } else {
-                if (hh <= 0 || ww <= 0 || hh % img || ww % img) throw std::invalid_argument("lr_forward: image_sizes must be positive multiples of the crop size");
-                const int hc = (int)(hh / img), wc = (int)(ww / img);
-                ncr = hc * wc + 1;
-                smp[b] = HdSample{hc, wc, NC, SV};
-                V = hc * g2 * (wc * g2 + 1) + 1 + g2 * (g2 + 1);
-            }
-            if (ncr > n_crops) throw std::invalid_argument("lr_forward: image_sizes needs more crops than pixel_values holds");
-            voff[b] = SV;
-            for (int c = 0; c < ncr; ++c) crop_src[NC++] = b * n_crops + c;
-            SV += V;
-            Vmax = V > Vmax ? V : Vmax;
-        }
-        voff[B] = SV;
-        LR_HIP_CHECK(hipMemcpyAsync(td, th, h->tab_bytes, hipMemcpyHostToDevice, st));
-        LR_HIP_CHECK(hipEventRecord(h->tab_ev[slot], st));
-        h->tab_used[slot] = true;
-        const int* d_crop_src = (const int*)td;
-        const HdSample* d_smp = (const HdSample*)(td + smp_off);
-        const LlavaSample* d_lsmp = (const LlavaSample*)(td + smp_off);
-        const int* d_voff = (const int*)(td + voff_off);
-        h->lastB = B; h->lastS = S; h->lastNC = NC; h->lastSV = SV; h->lastVmax = Vmax;
-        h->last_voff.assign(voff, voff + B + 1);
-
-        // ---- CLIP tower (utils/utils.py:266-273) ----
-        const int Rp = NC * (T - 1), Rc = NC * T;
-        const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision stage's operand form (covers the projector)
-        launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, img, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, fv.prec);
-        Operand pa = operand16(h->patchA, h->Kpad, Rp, fv);
-        linear(h, st, fv, Linear{h->patch_w, nullptr, Hc, h->Kpad, EPI_OUT_F32, ACT_NONE}, pa, h->patch_out);
-        launch_clip_embed(h->patch_out, h->cls, h->pos, h->pre_w, h->pre_b, h->clip_x, NC, T, Hc, d.clip_ln_eps, st);
-        const int ncl = h->lim_clip >= 0 && h->lim_clip < d.clip_layers ? h->lim_clip : d.clip_layers;
-        for (int l = 0; l < ncl; ++l) {
-            const ClipLayer& c = h->cl[l];
-            const Linear qkv{c.qkv_w, c.qkv_b, 3 * Hc, Hc, EPI_OUT_OP, ACT_NONE}, out{c.out_w, c.out_b, Hc, Hc, EPI_RESADD_F32, ACT_NONE},
-                         fc1{c.fc1_w, c.fc1_b, Mc, Hc, EPI_OUT_OP, ACT_QUICK_GELU}, fc2{c.fc2_w, c.fc2_b, Hc, Mc, EPI_RESADD_F32, ACT_NONE};
-            Operand n = norm_rows(h, st, fv, &qkv, h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
-            const Operand q = linear(h, st, fv, qkv, n, h->clip_qkv);
-            AttnParams ap{h->clip_qkv, h->clip_qkv, h->clip_qkv, h->clip_att, nullptr, nullptr, 0, 3 * Hc, Hc, 0, Hc, 2 * Hc, T, d.clip_heads, 0.125f, 1};
-            Operand att = apply_prec(h, fv, ap, q, Rc);
-            emulate_attention_lo8(h, fv, ap, Rc, d.clip_heads, 64, st);
-            launch_attention(ap, NC, 64, false, h->op_dt, st);
-            linear(h, st, fv, out, att, h->clip_x);
-            n = norm_rows(h, st, fv, &fc1, h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
-            Operand ff = linear(h, st, fv, fc1, n, h->clip_ff, &fc2);
-            linear(h, st, fv, fc2, ff, h->clip_x);
-        }
-        const Linear p0{h->p0_w, h->p0_b, D, h->llava ? Hc : 4 * Hc, EPI_OUT_OP, ACT_GELU_ERF}, p2{h->p2_w, h->p2_b, D, D, EPI_OUT_F32, ACT_NONE};
-        if (h->llava) {
-            // ---- per-token projector, then anyres packing (modeling_llava_next.py get_image_features/pack_image_features) ----
-            launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, fv.prec);
-            Operand a = operand16(h->hdA, Hc, Rp, fv);
-            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
-            linear(h, st, fv, p2, p1, h->pf32);
-            launch_llava_pack(h->pf32, d_lsmp, B, SV, h->G, D, h->newline, h->ev, st);
-        } else {
-            // ---- HD transform + projector (modeling_phi3_v.py:254-303) ----
-            launch_hd_gather(h->clip_x, d_smp, B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, fv.prec);
-            Operand a = operand16(h->hdA, 4 * Hc, SV, fv);
-            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
-            linear(h, st, fv, p2, p1, h->ev);
-        }
+        const int D = d.hidden;
+        const VisionPlan vp = run_vision(h, st, pixel_values, pix_dtype, image_sizes_host, B, S, n_crops, "lr_forward");
+        const int* d_voff = vp.d_voff; const int* voff = vp.voff; const int Vmax = vp.Vmax;
         // ---- embeddings, positions (modeling_phi3_v.py:228-249, rw_model:344-345 | llava: masked_scatter, arange positions) ----
         const int Rl = B * S;
         launch_token_plan(input_ids, attention_mask, B, S, d_voff, h->img_row, h->pos_ids, h->tstat, st,
@@ -694,22 +767,129 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
             LR_HIP_CHECK(hipGetLastError());
             return;
         }
-        // ---- tail: final norm of the gathered row, SkipCA, value head (rw_model:376-448) ----
-        // (after a gathered last layer the B rows are already compact in xg: S = 1, position 0)
-        launch_gather_norm_rows(h->last_pruned ? h->xg : h->x, h->tstat, h->last_pruned ? 1 : S, h->last_pruned ? 1 : last_pos,
-                                (flags & LR_FWD_NO_FINAL_NORM) ? nullptr : h->norm_w, d.rms_eps, h->hL, B, D, st);
-        const float* ao = nullptr;
-        if (d.add_cross_attention) {
-            launch_rowvec_linear(h->hL, h->Wq, h->tq, B, D, D, st);
-            launch_rowvec_linear(h->tq, h->WkT, h->tkq, B, D, D, st);
-            launch_ca_scores(h->ev, h->tkq, d_voff, B, Vmax, D, 1.0f / std::sqrt((float)D), h->tsc, st);
-            launch_ca_softmax(h->tsc, B, Vmax, st);
-            launch_ca_context(h->ev, h->tsc, d_voff, B, Vmax, D, h->tctx, st);
-            launch_rowvec_linear(h->tctx, h->Wv, h->tao, B, D, D, st);
-            ao = h->tao;
+        reward_tail(h, st, flags, S, h->ev, d_voff, 1, Vmax, B, rewards_out);
+        LR_HIP_CHECK(hipGetLastError());
+    });
+}
+
+size_t lr_prefix_bytes(lr_handle h, int n_shared, int n_image_tokens) {
+    if (!h || h->qwen || n_shared < 0 || n_image_tokens < 0) return 0;
+    return prefix_layout(h, n_shared, n_image_tokens).total;
+}
+
+int lr_prefix_build(lr_handle h, const int64_t* prefix_ids, int n_prefix, const void* pixel_values, int pix_dtype,
+                    const int64_t* image_size_host, int n_crops, int total_len, void* cache, size_t cache_bytes, lr_prefix_info* info,
+                    void* hip_stream) {
+    if (!h) return LR_EINVAL;
+    return guarded(h, [&] {
+        prefix_refuse_handle(h, "lr_prefix_build");
+        if (!prefix_ids || !pixel_values || !image_size_host || !cache || !info) throw std::invalid_argument("lr_prefix_build: null argument");
+        const lr_model_desc& d = h->d;
+        const int NS = n_prefix / 64 * 64;
+        if (total_len <= 0) total_len = n_prefix;
+        if (NS < 64) throw std::invalid_argument("lr_prefix_build: the prefix holds no whole 64-key tile (n_shared == 0): score such rows with lr_forward");
+        if (total_len < n_prefix || total_len > d.max_seq) throw std::invalid_argument("lr_prefix_build: total_len must lie in [n_prefix, max_seq]");
+        if (n_crops < 2 || n_crops > d.max_crops) throw std::invalid_argument("lr_prefix_build: n_crops exceeds max_crops");
+        if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_prefix_build: pixel dtype must be F32 or BF16");
+        if (((uintptr_t)cache) & 255) throw std::invalid_argument("lr_prefix_build: the cache must be 256-byte aligned");
+        hipStream_t st = (hipStream_t)hip_stream;
+        const int D = d.hidden;
+        const VisionPlan vp = run_vision(h, st, pixel_values, pix_dtype, image_size_host, 1, NS, n_crops, "lr_prefix_build");
+        const int V = vp.SV;
+        const PrefixLayout L = prefix_layout(h, NS, V);
+        if (cache_bytes < L.total) throw std::invalid_argument("lr_prefix_build: cache smaller than lr_prefix_bytes");
+        char* base = (char*)cache;
+        // the first n_shared prefix positions as ONE sequence, every token valid (mask == null)
+        launch_token_plan(prefix_ids, nullptr, 1, NS, vp.d_voff, h->img_row, h->pos_ids, h->tstat, st);
+        launch_prefix_header(h->tstat, V, (int*)base, st);
+        launch_embed(prefix_ids, h->img_row, h->wte, h->ev, h->x, NS, D, d.vocab_size, st);
+        const int rot = total_len + (d.rope_flash_convention ? 1 : 0);       // what lr_forward passes for a batch of that width
+        launch_rope_table(h->pos_ids, h->tstat, 1, NS, h->inv_s, h->inv_l, d.rope_scaling, d.orig_max_pos, h->half, h->cs, st, rot);
+        const float ascale = 1.0f / std::sqrt((float)h->hd);
+        const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
+        for (int l = 0; l < L.nl; ++l) {
+            const DecLayer& Ly = h->dl[l];
+            const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
+            const Linear qkv{Ly.qkv_w, Ly.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &Ly.lqkv, h->cs, Hq + Hkv, h->hd};
+            void* rows = base + L.layer[l];                 // the projection writes its rows straight into the cache
+            Operand n = norm_rows(h, st, fq, &qkv, h->x, Ly.ln1, nullptr, h->h, NS, D, d.rms_eps);
+            const Operand q = qkv_rope(h, st, fq, qkv, n, rows, h->qkv32, (size_t)d.max_batch * d.max_seq);
+            check_layout(q, fa, "attention");
+            if (l == L.nl - 1) break;                       // the last layer contributes K and V only
+            AttnParams ap{rows, rows, rows, h->att, nullptr, nullptr, 0, Nqkv, Hq, 0, Hq, Hq + Hkv, NS, d.heads, ascale, d.heads / d.kv_heads};
+            const Operand att = apply_prec(h, fa, ap, q, NS);
+            launch_attention(ap, 1, h->hd, true, h->op_dt, st);
+            decoder_tail(h, st, l, att, h->x, h->h, h->ff);
         }
-        launch_reward_head(h->hL, ao, h->ca_w, d.ca_eps, h->vh, d.value_head_dim, rewards_out, B, D, st);
-        launch_slot_check(h->tstat, d_voff, rewards_out, B, d.value_head_dim, st);
+        LR_HIP_CHECK(hipMemcpyAsync(base + L.ev, h->ev, (size_t)V * D * 4, hipMemcpyDeviceToDevice, st));
+        LR_HIP_CHECK(hipGetLastError());
+        h->lastB = 0; h->last_pruned = false;               // (no reward rows: the taps of a forward have nothing to show)
+        std::memset(info, 0, sizeof(*info));
+        info->struct_size = (int32_t)sizeof(*info);
+        info->n_prefix = n_prefix; info->n_shared = NS; info->n_image_tokens = V;
+        info->long_factors = rot > d.orig_max_pos ? 1 : 0;
+        info->n_layers = L.nl;
+        info->weights_epoch = h->weights_epoch;
+        info->form_signature = prefix_signature(h);
+        info->cache_bytes = L.total;
+    });
+}
+
+int lr_forward_prefixed(lr_handle h, const void* cache, const lr_prefix_info* info, const int64_t* input_ids, const int64_t* attention_mask,
+                        int B, int T, int flags, float* rewards_out, void* hip_stream) {
+    if (!h) return LR_EINVAL;
+    return guarded(h, [&] {
+        prefix_refuse_handle(h, "lr_forward_prefixed");
+        if (!cache || !info || !input_ids || !attention_mask || !rewards_out) throw std::invalid_argument("lr_forward_prefixed: null argument");
+        const lr_model_desc& d = h->d;
+        if (info->struct_size != (int32_t)sizeof(*info)) throw std::invalid_argument("lr_forward_prefixed: lr_prefix_info.struct_size mismatch");
+        if (flags & LR_FWD_KEEP_HIDDEN_STATES) throw std::logic_error("lr_forward_prefixed: LR_FWD_KEEP_HIDDEN_STATES needs the hidden states of the shared positions, which a prefix cache does not hold");
+        if (info->weights_epoch != h->weights_epoch)
+            throw std::logic_error("lr_forward_prefixed: stale prefix cache: the weights changed since it was built (lr_weights_epoch moved); build it again");
+        const int NS = info->n_shared, V = info->n_image_tokens;
+        const PrefixLayout L = prefix_layout(h, NS, V);
+        if (info->form_signature != prefix_signature(h) || info->n_layers != L.nl || info->cache_bytes != L.total)
+            throw std::logic_error("lr_forward_prefixed: stale prefix cache: the operand forms (precision map / sites), layer limits or kernel settings "
+                                   "changed since it was built; build it again");
+        if (B < 1 || B > d.max_batch) throw std::invalid_argument("lr_forward_prefixed: batch exceeds max_batch");
+        if (T < 1 || NS + T > d.max_seq) throw std::invalid_argument("lr_forward_prefixed: n_shared + T exceeds max_seq");
+        const int S = NS + T, rot = S + (d.rope_flash_convention ? 1 : 0);
+        if ((rot > d.orig_max_pos ? 1 : 0) != info->long_factors)
+            throw std::logic_error(std::string("lr_forward_prefixed: a batch of width n_shared + T = ") + std::to_string(S) + " takes the " +
+                                   (info->long_factors ? "short" : "long") + " su-RoPE factor set, the cache was built with the other one; build it again with total_len = that width");
+        hipStream_t st = (hipStream_t)hip_stream;
+        const int D = d.hidden, Rl = B * T;
+        const char* base = (const char*)cache;
+        const int* hdr = (const int*)base;                  // {0, V, image slots among the shared tokens}
+        const float* ev = (const float*)(base + L.ev);
+        // rows [tail of the prefix | caption | right padding]: positions continue at n_shared, the tail's image slots read the cached rows
+        launch_token_plan(input_ids, attention_mask, B, T, hdr, h->img_row, h->pos_ids, h->tstat, st, -1L, 0, NS, hdr + 2, 0);
+        launch_embed(input_ids, h->img_row, h->wte, ev, h->x, Rl, D, d.vocab_size, st);
+        launch_rope_table(h->pos_ids, h->tstat, B, T, h->inv_s, h->inv_l, d.rope_scaling, d.orig_max_pos, h->half, h->cs, st, rot);
+        const int last_pos = (flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0, gather = 1 + last_pos;
+        const float ascale = 1.0f / std::sqrt((float)h->hd);
+        const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
+        h->last_pruned = false;
+        for (int l = 0; l < L.nl; ++l) {
+            const DecLayer& Ly = h->dl[l];
+            const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
+            const Linear qkv{Ly.qkv_w, Ly.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &Ly.lqkv, h->cs, Hq + Hkv, h->hd};
+            Operand n = norm_rows(h, st, fq, &qkv, h->x, Ly.ln1, nullptr, h->h, Rl, D, d.rms_eps);
+            const Operand q = qkv_rope(h, st, fq, qkv, n, h->qkv, h->qkv32, (size_t)d.max_batch * d.max_seq);
+            AttnParams ap{h->qkv, h->qkv, h->qkv, h->att, attention_mask, nullptr, 0, Nqkv, Hq, 0, Hq, Hq + Hkv, T, d.heads, ascale, d.heads / d.kv_heads};
+            ap.Ks = ap.Vs = base + L.layer[l];
+            ap.n_shared = NS;
+            const bool pruned = l == L.nl - 1;              // the last layer runs for the row each reward is read from only (run_decoder_stack)
+            if (pruned) { ap.O = h->attg; ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = gather == 2 ? 1 : 0; }
+            const Operand att = apply_prec(h, fa, ap, q, pruned ? B : Rl);
+            launch_attention_shared(ap, B, h->hd, h->op_dt, st);
+            if (!pruned) { decoder_tail(h, st, l, att, h->x, h->h, h->ff); continue; }
+            launch_gather_norm_rows(h->x, h->tstat, T, gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);
+            decoder_tail(h, st, l, att, h->xg, h->hg, h->ffg);
+            h->last_pruned = true;
+        }
+        h->lastB = 0;                                       // (the taps of a forward describe whole rows; there are none here)
+        reward_tail(h, st, flags, T, ev, hdr, 0, V, B, rewards_out);
         LR_HIP_CHECK(hipGetLastError());
     });
 }
@@ -922,6 +1102,17 @@ int lr_op_attention_split_ex(const void* Q, const void* K, const void* V, void* 
         AttnParams p{Q, K, V, O, mask, kmin, 1, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group, nullptr, 0, lo_off, o_split};
         p.lazy_t = lazy_threshold;
         launch_attention(p, batch, head_dim, causal != 0, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+    });
+}
+
+int lr_op_attention_shared(const void* Q, const void* K, const void* V, const void* Ks, const void* Vs, void* O, const int64_t* mask,
+                           int n_shared, int ldq, int ldo, int qoff, int koff, int voff, int lo_off, int o_split, int batch, int S, int heads,
+                           int head_dim, int kv_group, float scale, float lazy_threshold, int operand_dtype, void* hip_stream) {
+    return op_guard([&] {
+        AttnParams p{Q, K, V, O, mask, nullptr, 0, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group, nullptr, 0, lo_off, o_split};
+        p.lazy_t = lazy_threshold;
+        p.Ks = Ks; p.Vs = Vs; p.n_shared = n_shared;
+        launch_attention_shared(p, batch, head_dim, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
     });
 }
 

@@ -25,6 +25,8 @@ int prepare_weight_e4m3(const void* w, int ldw, int K, int N, void* dst, int ope
 void launch_quantize_rows_fp8(const void* x, int ldx, int K, int rows, void* q, int ldq, float* scale, int operand_dtype, hipStream_t st);
 // attention.hip
 void launch_attention(const AttnParams& p, int batch, int head_dim, bool causal, int operand_dtype, hipStream_t st);
+// attention_shared.hip: the shared-key-prefix form (AttnParams::Ks / Vs / n_shared); causal, head_dim 96 or 128
+void launch_attention_shared(const AttnParams& p, int batch, int head_dim, int operand_dtype, hipStream_t st);
 
 // rowops.hip ------------------------------------------------------------------------------------
 // y_op[r][:] = LN(x[r][:]) * w + b   (b == null -> RMSNorm: x * rsqrt(mean x^2 + eps) * w)
@@ -43,9 +45,15 @@ void launch_clip_embed(const float* patch_out, const float* cls, const float* po
 // image slots: ids < 0 (Phi-3-V) when image_token_id < 0, else ids == image_token_id (LLaVA);
 // positions: cumsum(mask)-1 with pads -> 1 (rw_model:344-345) or arange(S) when pos_arange (no position_ids passed)
 void launch_token_plan(const int64_t* ids, const int64_t* mask, int B, int S, const int* voff, int* img_row, int* pos,
-                       int* tstat, hipStream_t st, long image_token_id = -1, int pos_arange = 0);
+                       int* tstat, hipStream_t st, long image_token_id = -1, int pos_arange = 0, int pos_base = 0,
+                       const int* img_base = nullptr, int voff_stride = 1);
+// rows that continue a shared prefix (lr_forward_prefixed): positions count from pos_base, image-slot ranks from *img_base (device:
+// the slots the prefix holds; tstat's slot count includes them), mask == null = every token valid.  voff_stride (here and in the
+// SkipCA / slot-check launchers below): 1 = row b reads image rows voff[b] .. voff[b + 1], 0 = every row reads voff[0] .. voff[1].
+// hdr[0..2] = {0, V, image slots among the prefix tokens (tstat[2] of a one-row token plan)}: the head of a prefix cache
+void launch_prefix_header(const int* tstat, int V, int* hdr, hipStream_t st);
 // rewards[b][:] = NaN where the image-slot count of row b (tstat) differs from its image-token count voff[b+1] - voff[b]
-void launch_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, hipStream_t st);
+void launch_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, hipStream_t st, int voff_stride = 1);
 // x[b*S+s] = img_row >= 0 ? ev[img_row] : wte[clamp(id)]
 void launch_embed(const int64_t* ids, const int* img_row, const unsigned short* wte_bf16, const float* ev, float* x,
                   int rows, int D, int vocab, hipStream_t st);
@@ -91,10 +99,10 @@ void launch_gather_norm_rows(const float* x, const int* tstat, int S, int use_la
                              float* y, int B, int D, hipStream_t st);
 void launch_rowvec_linear(const float* x, const float* W, float* y, int B, int N, int K, hipStream_t st);      // y[b] = W x[b], fp32
 void launch_ca_scores(const float* ev, const float* kq, const int* voff, int B, int Vmax, int D, float scale, float* sc,
-                      hipStream_t st);
+                      hipStream_t st, int voff_stride = 1);
 void launch_ca_softmax(float* sc, int B, int Vmax, hipStream_t st);
 void launch_ca_context(const float* ev, const float* pr, const int* voff, int B, int Vmax, int D, float* ctx,
-                       hipStream_t st);
+                       hipStream_t st, int voff_stride = 1);
 void launch_reward_head(const float* hL, const float* attn_o, const float* ca_w, float ca_eps, const float* vh, int d,
                         float* out, int B, int D, hipStream_t st);
 

@@ -313,15 +313,17 @@ void launch_clip_embed(const float* patch_out, const float* cls, const float* po
 __global__ __launch_bounds__(256) void token_plan_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask,
                                                          int S, const int* __restrict__ voff, int* __restrict__ img_row,
                                                          int* __restrict__ pos, int* __restrict__ tstat, long image_token_id,
-                                                         int pos_arange) {
+                                                         int pos_arange, int pos_base, const int* __restrict__ img_base, int vs) {
     __shared__ int wsum[2][4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int run_m = 0, run_n = 0, last = -1, first = S;
+    // rows that continue a shared prefix (lr_forward_prefixed): positions start at pos_base, image slots at rank *img_base (the
+    // slots the prefix holds), and every row reads the ONE image whose rows are voff[0] .. voff[1] (vs == 0); mask == null: all valid
+    int run_m = 0, run_n = img_base ? *img_base : 0, last = -1, first = S;
     for (int base = 0; base < S; base += 256) {
         const int s = base + tid;
         bool m = false, n = false;
         if (s < S) {
-            m = mask[(size_t)b * S + s] != 0;
+            m = mask ? mask[(size_t)b * S + s] != 0 : true;
             const int64_t id = ids[(size_t)b * S + s];
             n = image_token_id >= 0 ? (id == image_token_id) : (id < 0 && id > -1000000000LL);
         }
@@ -337,10 +339,10 @@ __global__ __launch_bounds__(256) void token_plan_kernel(const int64_t* __restri
             tm += wsum[0][w]; tn += wsum[1][w];
         }
         if (s < S) {
-            pos[(size_t)b * S + s] = pos_arange ? s : (m ? (om + pm) : 1);     // arange | cumsum(mask) - 1, pads -> 1
+            pos[(size_t)b * S + s] = pos_arange ? s : (m ? (pos_base + om + pm) : 1);     // arange | cumsum(mask) - 1, pads -> 1
             // a slot beyond the image tokens this row's image_sizes produce would read another row's features (or past the buffer):
             // it keeps the text embedding instead, and slot_check_kernel turns the row's reward into NaN
-            img_row[(size_t)b * S + s] = (n && on + pn < voff[b + 1] - voff[b]) ? (voff[b] + on + pn) : -1;
+            img_row[(size_t)b * S + s] = (n && on + pn < voff[b * vs + 1] - voff[b * vs]) ? (voff[b * vs] + on + pn) : -1;
             if (m) { last = s; if (s < first) first = s; }
         }
         run_m += tm; run_n += tn;
@@ -363,24 +365,32 @@ __global__ __launch_bounds__(256) void token_plan_kernel(const int64_t* __restri
 }
 
 void launch_token_plan(const int64_t* ids, const int64_t* mask, int B, int S, const int* voff, int* img_row, int* pos,
-                       int* tstat, hipStream_t st, long image_token_id, int pos_arange) {
+                       int* tstat, hipStream_t st, long image_token_id, int pos_arange, int pos_base, const int* img_base, int voff_stride) {
     if (B <= 0) return;
-    hipLaunchKernelGGL(token_plan_kernel, dim3(B), dim3(256), 0, st, ids, mask, S, voff, img_row, pos, tstat, image_token_id, pos_arange);
+    hipLaunchKernelGGL(token_plan_kernel, dim3(B), dim3(256), 0, st, ids, mask, S, voff, img_row, pos, tstat, image_token_id, pos_arange,
+                       pos_base, img_base, voff_stride);
 }
 
 // The reference fails such a batch (index_put shape mismatch, modeling_phi3_v.py:247; "Image features and image tokens do not
 // match", modeling_llava_next.py); the Python wrapper raises the same errors before the launch.  For direct C-ABI callers, who
 // get no host-side check (it would cost a device sync per pass), a row whose image-slot count differs from the number of image
 // tokens its image_sizes produce comes back as NaN instead of a silently wrong reward.
-__global__ void slot_check_kernel(const int* __restrict__ tstat, const int* __restrict__ voff, float* __restrict__ rewards, int B, int d) {
+__global__ void slot_check_kernel(const int* __restrict__ tstat, const int* __restrict__ voff, float* __restrict__ rewards, int B, int d, int vs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * d) return;
     const int b = i / d;
-    if (tstat[b * 4 + 2] != voff[b + 1] - voff[b]) rewards[i] = __builtin_nanf("");
+    if (tstat[b * 4 + 2] != voff[b * vs + 1] - voff[b * vs]) rewards[i] = __builtin_nanf("");
 }
-void launch_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, hipStream_t st) {
+void launch_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, hipStream_t st, int voff_stride) {
     if (B <= 0) return;
-    hipLaunchKernelGGL(slot_check_kernel, dim3(cdiv(B * d, 64)), dim3(64), 0, st, tstat, voff, rewards, B, d);
+    hipLaunchKernelGGL(slot_check_kernel, dim3(cdiv(B * d, 64)), dim3(64), 0, st, tstat, voff, rewards, B, d, voff_stride);
+}
+
+__global__ void prefix_header_kernel(const int* __restrict__ tstat, int V, int* __restrict__ hdr) {
+    if (threadIdx.x == 0) { hdr[0] = 0; hdr[1] = V; hdr[2] = tstat[2]; }
+}
+void launch_prefix_header(const int* tstat, int V, int* hdr, hipStream_t st) {
+    hipLaunchKernelGGL(prefix_header_kernel, dim3(1), dim3(64), 0, st, tstat, V, hdr);
 }
 
 // --------------------------------------------------------------------------------------- embedding
@@ -644,14 +654,14 @@ void launch_rowvec_linear(const float* x, const float* W, float* y, int B, int N
 // with modeling_phi3_v.py:245); they take part in the softmax un-masked.
 __global__ __launch_bounds__(256) void ca_scores_kernel(const float* __restrict__ ev, const float* __restrict__ kq,
                                                         const int* __restrict__ voff, int Vmax, int D, float scale,
-                                                        float* __restrict__ sc) {
+                                                        float* __restrict__ sc, int vs) {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
     const int lane = threadIdx.x & 63;
     if (j >= Vmax) return;
-    const int vb = voff[b + 1] - voff[b];
+    const int vb = voff[b * vs + 1] - voff[b * vs];
     float s = 0.f;
     if (j < vb) {
-        const float4* e = (const float4*)(ev + ((size_t)voff[b] + j) * D);
+        const float4* e = (const float4*)(ev + ((size_t)voff[b * vs] + j) * D);
         const float4* q = (const float4*)(kq + (size_t)b * D);
         for (int c = lane; c < (D >> 2); c += 64) {
             const float4 a = e[c], w = q[c];
@@ -663,9 +673,9 @@ __global__ __launch_bounds__(256) void ca_scores_kernel(const float* __restrict_
 }
 
 void launch_ca_scores(const float* ev, const float* kq, const int* voff, int B, int Vmax, int D, float scale, float* sc,
-                      hipStream_t st) {
+                      hipStream_t st, int voff_stride) {
     if (B <= 0 || Vmax <= 0) return;
-    hipLaunchKernelGGL(ca_scores_kernel, dim3(cdiv(Vmax, 4), B), dim3(256), 0, st, ev, kq, voff, Vmax, D, scale, sc);
+    hipLaunchKernelGGL(ca_scores_kernel, dim3(cdiv(Vmax, 4), B), dim3(256), 0, st, ev, kq, voff, Vmax, D, scale, sc, voff_stride);
 }
 
 __device__ __forceinline__ float block_reduce(float v, bool is_max, float* sh) {
@@ -699,11 +709,11 @@ void launch_ca_softmax(float* sc, int B, int Vmax, hipStream_t st) {
 
 __global__ __launch_bounds__(256) void ca_context_kernel(const float* __restrict__ ev, const float* __restrict__ pr,
                                                          const int* __restrict__ voff, int Vmax, int D,
-                                                         float* __restrict__ ctx) {
+                                                         float* __restrict__ ctx, int vs) {
     const int d = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (d >= D) return;
-    const int vb = voff[b + 1] - voff[b];
-    const float* e = ev + (size_t)voff[b] * D + d;
+    const int vb = voff[b * vs + 1] - voff[b * vs];
+    const float* e = ev + (size_t)voff[b * vs] * D + d;
     const float* p = pr + (size_t)b * Vmax;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     int j = 0;
@@ -718,9 +728,9 @@ __global__ __launch_bounds__(256) void ca_context_kernel(const float* __restrict
 }
 
 void launch_ca_context(const float* ev, const float* pr, const int* voff, int B, int Vmax, int D, float* ctx,
-                       hipStream_t st) {
+                       hipStream_t st, int voff_stride) {
     if (B <= 0) return;
-    hipLaunchKernelGGL(ca_context_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, ev, pr, voff, Vmax, D, ctx);
+    hipLaunchKernelGGL(ca_context_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, st, ev, pr, voff, Vmax, D, ctx, voff_stride);
 }
 
 // reward[b][k] = value_head[k] . (attn_o ? RMSNorm_ca(hL + attn_o) : hL)       (rw_model:386,408/427)

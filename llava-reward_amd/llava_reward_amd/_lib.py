@@ -53,6 +53,16 @@ class ModelDesc(C.Structure):
     ]
 
 
+class PrefixInfo(C.Structure):
+    """lr_prefix_info: what a shared-prefix cache was built from (lr_prefix_build fills it, lr_forward_prefixed checks it)."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_prefix", C.c_int32), ("n_shared", C.c_int32), ("n_image_tokens", C.c_int32),
+        ("long_factors", C.c_int32), ("n_layers", C.c_int32),
+        ("weights_epoch", C.c_uint64), ("form_signature", C.c_uint64), ("cache_bytes", C.c_uint64),
+    ]
+
+
 _lib = None
 
 _SIGS = {
@@ -71,6 +81,11 @@ _SIGS = {
                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lr_forward_qwen": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64),
                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "lr_prefix_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "lr_prefix_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_void_p,
+                                  C.c_size_t, C.POINTER(PrefixInfo), C.c_void_p]),
+    "lr_forward_prefixed": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PrefixInfo), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_void_p]),
     "lr_last_hidden_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "lr_vision_embeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_void_p]),
     "lr_read_tap": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -87,6 +102,7 @@ _SIGS = {
     "lr_op_attention": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 11 + [C.c_float, C.c_int, C.c_void_p]),
     "lr_op_attention_split": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 13 + [C.c_float, C.c_int, C.c_void_p]),
     "lr_op_attention_split_ex": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 13 + [C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "lr_op_attention_shared": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 13 + [C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "lr_op_attention_segments": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_int32)] + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_void_p]),
     "lr_op_attention_segments_split": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(C.c_int32)] + [C.c_int] * 10 + [C.c_float, C.c_float, C.c_int, C.c_void_p]),
     "lr_op_quantize_rows_fp8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -195,6 +195,59 @@ class RewardEngine:
             t.record_stream(torch.cuda.current_stream(dev))
         return out
 
+    # ------------------------------------------------------------------ shared image prefix (lr_prefix_build / lr_forward_prefixed)
+    def prefix_build(self, prefix_ids: torch.Tensor, pixel_values: torch.Tensor, image_size, total_len: int = 0):
+        """Cache of the first len(prefix_ids) // 64 * 64 positions of a prompt prefix that holds ONE image (lr_prefix_build).
+        Returns (cache: uint8 device tensor, info: _lib.PrefixInfo).  total_len: the width n_shared + T of the batches it will serve."""
+        dev = torch.device("cuda", self.device)
+        ids = prefix_ids.reshape(-1).to(dev, torch.int64).contiguous()
+        if pixel_values.dtype == torch.bfloat16:
+            pdt = L.LR_DT_BF16
+        else:
+            pixel_values, pdt = pixel_values.to(torch.float32), L.LR_DT_F32
+        pix = pixel_values.to(dev).contiguous()
+        if pix.dim() == 4:
+            pix = pix.unsqueeze(0)
+        if pix.dim() != 5 or pix.shape[0] != 1:
+            raise ValueError("pixel_values must be [1, crops, 3, H, W]: one image per prefix")
+        size = torch.as_tensor(image_size).to("cpu", torch.int64).reshape(-1).contiguous()
+        if size.numel() != 2:
+            raise ValueError("image_sizes must hold one (h, w)")
+        n_prefix = int(ids.numel())
+        n_img = int((ids < 0).sum())              # one host read per prefix: sizes the cache
+        nbytes = int(self.lib.lr_prefix_bytes(self.h, n_prefix // 64 * 64, n_img))
+        cache = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        info = L.PrefixInfo()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lr_prefix_build(self.h, C.c_void_p(ids.data_ptr()), n_prefix, C.c_void_p(pix.data_ptr()), pdt,
+                                      C.cast(size.data_ptr(), C.POINTER(C.c_int64)), pix.shape[1], int(total_len), C.c_void_p(cache.data_ptr()),
+                                      cache.numel(), C.byref(info), C.c_void_p(stream))
+        L.check(self.lib, rc, self.h, "lr_prefix_build")
+        for t in (ids, pix):
+            t.record_stream(torch.cuda.current_stream(dev))
+        return cache, info
+
+    def forward_prefixed(self, cache: torch.Tensor, info, input_ids: torch.Tensor, attention_mask: torch.Tensor, training: bool = False,
+                         out: Optional[torch.Tensor] = None, no_final_norm: bool = False) -> torch.Tensor:
+        """Rewards of RIGHT-padded rows [B, T] that hold what follows the cached positions (lr_forward_prefixed)."""
+        dev = torch.device("cuda", self.device)
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        mask = attention_mask.to(dev, torch.int64).contiguous()
+        if ids.dim() != 2 or ids.shape != mask.shape:
+            raise ValueError("input_ids and attention_mask must be [B, T]")
+        B, T = ids.shape
+        if out is None:
+            out = torch.empty(B, self.cfg.value_head_dim, device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self.lib.lr_forward_prefixed(self.h, C.c_void_p(cache.data_ptr()), C.byref(info), C.c_void_p(ids.data_ptr()),
+                                          C.c_void_p(mask.data_ptr()), B, T,
+                                          (L.LR_FWD_TRAINING_LAST_TOKEN if training else 0) | (L.LR_FWD_NO_FINAL_NORM if no_final_norm else 0),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        L.check(self.lib, rc, self.h, "lr_forward_prefixed")
+        for t in (ids, mask, cache):
+            t.record_stream(torch.cuda.current_stream(dev))
+        return out
+
     def forward_qwen(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: torch.Tensor,
                      image_grid_thw, training: bool = False, out: Optional[torch.Tensor] = None,
                      keep_hidden_states: bool = False) -> torch.Tensor:

@@ -101,6 +101,22 @@ class _LazyHiddenStates:
         return (self[i] for i in range(len(self)))
 
 
+class PrefixState:
+    """What RewardModel.build_prefix returns: the device cache of a prompt prefix that holds one image (per decoder layer the key /
+    value rows of its first n_shared = n_prefix // 64 * 64 positions, and the projected image rows) and the record of what it was
+    built from.  forward_prefixed refuses it once the weights, the operand forms or the layer limit have changed since."""
+
+    def __init__(self, cache, info, engine, layer_limit):
+        self.cache, self.info, self.engine, self.layer_limit = cache, info, engine, layer_limit
+        self.n_prefix, self.n_shared = int(info.n_prefix), int(info.n_shared)
+        self.n_image_tokens = int(info.n_image_tokens)
+        self.long_factors = bool(info.long_factors)
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.info.cache_bytes)
+
+
 class RewardModel:
     def __init__(self, cfg, weights: Optional[Dict[str, torch.Tensor]] = None, synth_seed: Optional[int] = None,
                  max_batch: int = 32, max_seq: int = 2816, max_crops: int = 17, operand_dtype: str = "f16x2f8",
@@ -411,6 +427,48 @@ class RewardModel:
                                      keep_hidden_states=return_output or self.keep_hidden_states)
         return self._finish(reward, input_ids.shape, return_output, inner,
                             lazy_args=(input_ids, attention_mask, pixel_values, sz) if return_output and not inner else None)
+
+    # -- N captions of one image: the image prefix once, then only what follows it --
+    def _prefix_guard(self, what: str):
+        if self.engine is None:
+            raise RuntimeError(f"{what}: model is on CPU; call model.to('cuda') first (the scoring path has no CPU fallback)")
+        if self.model_type != "phi3v":
+            raise NotImplementedError(f"{what}: the shared image prefix serves the Phi-3.5-V backbone; this is a {self.model_type} model "
+                                      "(score its rows with custom_forward)")
+        if self.mean_hidden_state:
+            raise NotImplementedError(f"{what}: mean_hidden_state pools every token of a row, the shared ones included; "
+                                      "not served from a prefix cache")
+        if not self._in_probe and self._form_epoch != self.engine.weights_epoch():
+            self._lock_operand_form()         # the step custom_forward takes: weights changed since the form was locked
+        inner = self.layer_id != 32 and self.layer_id < self.config.layers
+        self.engine.set_layer_limits(-1, self.layer_id if inner else -1)
+        return inner
+
+    def uses_long_factors(self, total_len: int) -> bool:
+        """Whether a batch of width total_len runs the long su-RoPE factor set (what custom_forward decides from its S)."""
+        return int(total_len) + (1 if getattr(self.config, "rope_flash_convention", False) else 0) > int(self.config.orig_max_pos)
+
+    def build_prefix(self, prefix_ids, pixel_values, image_sizes, total_len=None) -> PrefixState:
+        """Runs the vision tower, the projector and the decoder once over the first n_shared = len(prefix_ids) // 64 * 64 tokens of
+        `prefix_ids` (1-D, the image slots among them; pixel_values [1, crops, 3, 336, 336], image_sizes [1, 2]) and keeps what rows
+        that continue this prefix need.  total_len: width n_shared + T of the batches to come (selects the su-RoPE factor set)."""
+        self._prefix_guard("build_prefix")
+        ids = torch.as_tensor(prefix_ids).reshape(-1)
+        cache, info = self.engine.prefix_build(ids, pixel_values, torch.as_tensor(image_sizes).cpu().long(),
+                                               int(total_len) if total_len is not None else int(ids.numel()))
+        return PrefixState(cache, info, self.engine, self.layer_id)
+
+    def forward_prefixed(self, state: PrefixState, input_ids, attention_mask):
+        """custom_forward for rows that continue `state`'s prefix: input_ids / attention_mask [B, T], RIGHT-padded, hold everything behind
+        its first n_shared tokens.  Returns (reward, None) with custom_forward's conventions; the rewards are bit-identical to
+        custom_forward on the full right-padded rows with the image repeated per row."""
+        inner = self._prefix_guard("forward_prefixed")
+        if state.engine is not self.engine:
+            raise RuntimeError("forward_prefixed: stale prefix cache: the model moved to another device since it was built; build it again")
+        if input_ids.dim() == 3:
+            input_ids = input_ids.squeeze(1)
+        reward = self.engine.forward_prefixed(state.cache, state.info, input_ids, attention_mask, training=self.training, no_final_norm=inner)
+        return self._finish(reward, input_ids.shape, False, inner)
 
     def _finish(self, reward, shape, return_output, inner=False, lazy_args=None):
         """Return convention of rw_model:407-448.  Train mode without mean pooling reads the LAST position (left-padded batches) and

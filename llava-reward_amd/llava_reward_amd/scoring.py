@@ -177,6 +177,88 @@ def score_candidates(model, tokenizer, captions, images, num_crops: int = 16, ba
     return gather_rewards(torch.cat(out, dim=0), n)
 
 
+def plan_shared_prefix(rows_ids) -> Tuple[int, int]:
+    """(n_prefix, n_shared) of rows of token ids (1-D tensors or lists; image slots are negative ids): the longest token prefix all
+    rows share, and that length floored to the attention kernel's 64-key tile -- what a prefix cache can hold.  The rows' image slots
+    must be part of what they share: rows whose image-slot runs differ, or a row with a slot behind the common prefix, raise."""
+    rows = [[int(v) for v in (r.reshape(-1).tolist() if torch.is_tensor(r) else r)] for r in rows_ids]
+    if not rows:
+        raise ValueError("plan_shared_prefix: no rows")
+    n = min(len(r) for r in rows)
+    first = rows[0]
+    for r in rows[1:]:
+        k = 0
+        while k < n and r[k] == first[k]:
+            k += 1
+        n = k
+    slots = [[i for i, v in enumerate(r) if v < 0] for r in rows]
+    if any(s != slots[0] for s in slots[1:]):
+        raise ValueError(f"plan_shared_prefix: the rows' image-slot runs differ (slots per row {[len(s) for s in slots]}): "
+                         "they do not show the same image at the same place")
+    if slots[0] and slots[0][-1] >= n:
+        raise ValueError(f"plan_shared_prefix: a row holds an image slot at position {slots[0][-1]}, outside the common prefix of {n} tokens")
+    return n, n // 64 * 64
+
+
+@torch.no_grad()
+def score_captions(model, tokenizer, image, captions, num_crops: int = 16, batch_size: int = 32, pad_token_id: Optional[int] = None,
+                   device=None) -> torch.Tensor:
+    """Rewards of N captions of ONE image, [N, value_head_dim] fp32 on the model's device, in input order: ranking candidate captions
+    (or perspective questions) for an image.  Every prompt is `<|user|>\\n<|image_1|>\\n{caption}` (inference_process_phi3v), so the
+    rows share the image and everything in front of the caption: the HD transform, the vision tower, the projector and the decoder
+    over those positions run ONCE (RewardModel.build_prefix), then each batch runs only its captions against the cached keys and
+    values (forward_prefixed) -- bit-identical to custom_forward on the same rows, right-padded.  The prefix is rebuilt when a batch's
+    width selects the other su-RoPE factor set; rows that share fewer than 64 tokens take the ordinary forward.  Phi-3.5-V backbone.
+    With torch.distributed initialised the captions are sharded by rows and the rewards all-gathered."""
+    from .preprocess import _load_rgb, collate_rows, hd_transform_batch, merge_text_and_image_slots
+    if getattr(model, "model_type", "phi3v") != "phi3v":
+        raise NotImplementedError("score_captions builds Phi-3.5-V inputs; use the model's own processor + custom_forward(inputs_batch=...)")
+    caps = list(captions)
+    n = len(caps)
+    rank, ws = world()
+    device = device or model.device
+    d = int(getattr(model, "value_head_dim", 1))
+    if n == 0:
+        return torch.empty((0, d), dtype=torch.float32, device=device)
+    pix, sizes, ntok = hd_transform_batch([_load_rgb(image)], num_crops, device)
+    rows_ids = []
+    for caption in caps:
+        msg = {"role": "user", "content": f"<|image_1|>\n{caption}"}
+        prompt = tokenizer.apply_chat_template([msg], tokenize=False, add_generation_prompt=True)[:-22] + tokenizer.eos_token
+        rows_ids.append(merge_text_and_image_slots(tokenizer, prompt, [ntok[0]])[0][0])
+    n_prefix, n_shared = plan_shared_prefix(rows_ids)          # over ALL rows: every rank plans the same split
+    pad = pad_token_id if pad_token_id is not None else tokenizer.pad_token_id
+    rows = shard_rows(n, rank, ws)
+    was_training = bool(getattr(model, "training", False))
+    if was_training:
+        model.eval()                     # the EOS-position convention of inference (rw_model:416-425)
+    out = [torch.empty((0, d), dtype=torch.float32, device=device)]
+    state = None
+    try:
+        for lo in range(rows.start, rows.stop, batch_size):
+            hi = min(lo + batch_size, rows.stop)
+            part = rows_ids[lo:hi]
+            if n_shared == 0:            # nothing to share: the ordinary forward on the left-padded batch
+                batch = collate_rows([{"input_ids": r.unsqueeze(0).to(device), "attention_mask": torch.ones(1, len(r), dtype=torch.long, device=device),
+                                       "pixel_values": pix, "image_sizes": sizes} for r in part], pad)
+                out.append(model.custom_forward(**batch)[0].float().reshape(hi - lo, d))
+                continue
+            T = max(len(r) for r in part) - n_shared
+            if state is None or state.long_factors != model.uses_long_factors(n_shared + T):
+                state = model.build_prefix(rows_ids[lo][:n_prefix], pix, sizes, total_len=n_shared + T)
+            ids = torch.full((hi - lo, T), int(pad), dtype=torch.long)
+            mask = torch.zeros((hi - lo, T), dtype=torch.long)
+            for i, r in enumerate(part):
+                k = len(r) - n_shared
+                ids[i, :k] = r[n_shared:]
+                mask[i, :k] = 1
+            out.append(model.forward_prefixed(state, ids.to(device), mask.to(device))[0].float().reshape(hi - lo, d))
+    finally:
+        if was_training:
+            model.train()
+    return gather_rewards(torch.cat(out, dim=0), n)
+
+
 @torch.no_grad()
 def score_pairwise(model, args, batches: Iterable, device=None) -> Dict[str, object]:
     """batches yields (inputs_c, inputs_r, c_rates, r_rates) as the reference's DataLoader does.
