@@ -181,6 +181,9 @@ struct lr_engine {
     int layer_form(int l) const { return (pm_mid >= 0 && l >= pm_first && l < d.layers - pm_last) ? pm_mid : -1; }
     int site_form(int l, int site) const { const int f = layer_form(l); return (f >= 0 && pm_site[site] >= 0) ? pm_site[site] : f; }
     Form site(int l, int s) const { return form(site_form(l, s)); }
+    // lr_set_layer_limits: how many decoder layers / layers of a `depth`-layer vision tower a pass runs
+    int n_layers() const { return lim_layers >= 0 && lim_layers < d.layers ? lim_layers : d.layers; }
+    int n_tower_layers(int depth) const { return lim_clip >= 0 && lim_clip < depth ? lim_clip : depth; }
 
     void* dalloc(size_t bytes, bool weight) {
         void* p = nullptr;
@@ -295,6 +298,31 @@ inline void upload_rope_tables(lr_engine* e) {
     LR_HIP_CHECK(hipMemcpy(e->inv_l, e->d.inv_freq_long, sizeof(e->d.inv_freq_long), hipMemcpyHostToDevice));
 }
 
+
+// One slot of the per-forward table ring: taking it waits until the pass that used it NSLOT passes ago has read it (bounds host
+// run-ahead to NSLOT passes); the caller fills host(), commit() mirrors it to dev() on st.
+struct TableSlot {
+    lr_engine* h; int i;
+    explicit TableSlot(lr_engine* e) : h(e), i(e->slot_i) {
+        e->slot_i = (i + 1) % lr_engine::NSLOT;
+        if (e->tab_used[i]) LR_HIP_CHECK(hipEventSynchronize(e->tab_ev[i]));
+    }
+    char* host() const { return h->tab_host + (size_t)i * h->tab_bytes; }
+    char* dev() const { return h->tab_dev + (size_t)i * h->tab_bytes; }
+    void commit(hipStream_t st) const {
+        LR_HIP_CHECK(hipMemcpyAsync(dev(), host(), h->tab_bytes, hipMemcpyHostToDevice, st));
+        LR_HIP_CHECK(hipEventRecord(h->tab_ev[i], st));
+        h->tab_used[i] = true;
+    }
+};
+
+// Argument checks the entry points share; who = the entry's name, the prefix of its message.
+inline void require(bool ok, const char* who, const char* what) { if (!ok) throw std::invalid_argument(std::string(who) + what); }
+inline void check_batch(const lr_engine* h, int B, const char* who) { require(B >= 1 && B <= h->d.max_batch, who, ": batch exceeds max_batch"); }
+inline void check_seq(const lr_engine* h, int S, const char* who) { require(S >= 1 && S <= h->d.max_seq, who, ": sequence exceeds max_seq"); }
+inline void check_crops(const lr_engine* h, int n, const char* who) { require(n >= 2 && n <= h->d.max_crops, who, ": n_crops exceeds max_crops"); }
+inline void check_pix_dtype(int dt, const char* who) { require(dt == LR_DT_F32 || dt == LR_DT_BF16, who, ": pixel dtype must be F32 or BF16"); }
+inline int op_dtype(int lr_dt) { return lr_dt == LR_DT_F16 ? DT_F16 : DT_BF16; }      // LR_DT_* of an operand -> DT_*
 
 template <typename F> int guarded(lr_engine* e, F&& f) {
     try {
@@ -603,12 +631,32 @@ inline void register_lora(lr_engine* e, Lora& L, const std::string& mod, int N_f
 }
 
 
-// engine.hip: pre-norm decoder stack shared by the three backbones (x, cs, tstat prepared by the caller).
+// ---- shared image prefix: layout of a cache ----
+// [256-byte head: int {0, V, image slots among the shared tokens} | per decoder layer l < nl: the qkv rows of the n_shared shared
+//  positions exactly as that layer's attention site reads them (post-RoPE, [hi | lo] where the site's form is split; the row stride of
+//  the qkv buffer, so the attention kernel's per-thread offsets serve both sources) | ev: V projected image rows, fp32]
+struct PrefixLayout { std::vector<size_t> layer; size_t ev = 0, total = 0; int nl = 0; };
+
+// engine.hip: THE pre-norm decoder pass of the three backbones and the two prefix entries (x, cs, tstat prepared by the caller) over B
+// sequences of S rows; mask [B, S] or null (every row valid).
 // gather: 0 = every row through every layer; 1 / 2 = only the row of each sequence the reward is read from is wanted afterwards
 // (1: its last valid position, tstat[4 b]; 2: position S - 1): the LAST layer then runs its attention, o_proj and MLP for those B
 // rows only (rw_model:408-421 reads one row per sample) and leaves them in h->xg [B, hidden]; returns true when it did.
-bool run_decoder_stack(lr_engine* h, hipStream_t st, const int64_t* attention_mask, int B, int S, int gather = 0);
+// KV sink (kv_out): layer l's projection writes its rows to kv_out + layout->layer[l] instead of h->qkv, its attention reads them there,
+// and the last layer stops behind its projection.  KV prefix (kv_shared): the n_shared rows at kv_shared + layout->layer[l] sit in
+// front of every sequence's own keys.  A pass with neither alone passes the first valid key (tstat + 1) and runs LR_ATT_EMU_LO8.
+struct DecoderPass {
+    const int64_t* mask; int B, S;
+    int gather = 0;
+    const PrefixLayout* layout = nullptr;
+    char* kv_out = nullptr;
+    const char* kv_shared = nullptr; int n_shared = 0;
+};
+bool run_decoder_stack(lr_engine* h, hipStream_t st, const DecoderPass& p);
 void alloc_gather_ws(lr_engine* h);
+// engine.hip, for both finalizers: the decoder's workspace of Rl rows (x .. cs, lt, pos_ids, img_row, in this order) and its e4m3-twin entries
+void alloc_decoder_ws(lr_engine* h, size_t Rl);
+void push_decoder_weights(const lr_engine* h, std::vector<GemmWeight>& ws, size_t Rl);
 // engine.hip: rw_model:398-406 -- SkipCA for every token (o: per-token term, u: per-sample term, either may be null), masked mean
 // pooling into h->hL, value head.  Vb / voff: image rows of every sample in h->ev (host), Vmax = their maximum.
 void run_mean_pool_head(lr_engine* h, hipStream_t st, const int64_t* attention_mask, int B, int S, const int* voff_host, int Vmax,

@@ -218,37 +218,62 @@ static void decoder_tail(lr_engine* h, hipStream_t st, int l, Operand att, float
     linear(h, st, fd, down, f, x);
 }
 
-bool run_decoder_stack(lr_engine* h, hipStream_t st, const int64_t* attention_mask, int B, int S, int gather) {
+bool run_decoder_stack(lr_engine* h, hipStream_t st, const DecoderPass& p) {
     const lr_model_desc& d = h->d;
-    const int D = d.hidden, Rl = B * S;
-    const int nl = h->lim_layers >= 0 && h->lim_layers < d.layers ? h->lim_layers : d.layers;
+    const int D = d.hidden, B = p.B, S = p.S, Rl = B * S, nl = h->n_layers();
     const float ascale = 1.0f / std::sqrt((float)h->hd);
     const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
+    const bool own = !p.kv_out && !p.kv_shared;        // every key of a sequence is one of this pass's rows in h->qkv
     for (int l = 0; l < nl; ++l) {
         const DecLayer& L = h->dl[l];
         // the operand form of every site of this layer (lr_set_precision_map / lr_set_precision_sites): handed to the site's
         // producer and to its consumer
         const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
         const Linear qkv{L.qkv_w, L.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &L.lqkv, h->cs, Hq + Hkv, h->hd};
+        void* rows = p.kv_out ? p.kv_out + p.layout->layer[l] : h->qkv;       // (sink: the projection writes straight into the cache)
         Operand n = norm_rows(h, st, fq, &qkv, h->x, L.ln1, nullptr, h->h, Rl, D, d.rms_eps);
-        const Operand q = qkv_rope(h, st, fq, qkv, n, h->qkv, h->qkv32, (size_t)d.max_batch * d.max_seq);
-        AttnParams ap{h->qkv, h->qkv, h->qkv, h->att, attention_mask, h->tstat + 1, 4, Nqkv, Hq, 0, Hq, Hq + Hkv, S, d.heads, ascale,
-                      d.heads / d.kv_heads};
+        const Operand q = qkv_rope(h, st, fq, qkv, n, rows, h->qkv32, (size_t)d.max_batch * d.max_seq);
+        if (p.kv_out && l == nl - 1) { check_layout(q, fa, "attention"); break; }      // a sink's last layer contributes K and V only
+        AttnParams ap{rows, rows, rows, h->att, p.mask, own ? h->tstat + 1 : nullptr, own ? 4 : 0, Nqkv, Hq, 0, Hq, Hq + Hkv, S, d.heads,
+                      ascale, d.heads / d.kv_heads};
+        if (p.kv_shared) { ap.Ks = ap.Vs = p.kv_shared + p.layout->layer[l]; ap.n_shared = p.n_shared; }
         // Last layer: every row still feeds K and V, but only one row per sequence is read afterwards (rw_model:408-421).  Its
         // query sits in the qkv rows as usual; the attention kernel runs the one query tile that holds it (same arithmetic as
         // in the full launch) and stores B rows; the residual rows are gathered and o_proj / norm / MLP run on M = B rows --
         // the GEMM kernels never look at M when they pick their form, so these rows come out bit-identical to a full layer.
-        const bool pruned = gather && l == nl - 1;
-        if (pruned) { ap.O = h->attg; ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = gather == 2 ? 1 : 0; }
+        const bool pruned = p.gather && l == nl - 1;
+        if (pruned) { ap.O = h->attg; ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = p.gather == 2 ? 1 : 0; }
         const Operand att = apply_prec(h, fa, ap, q, pruned ? B : Rl);
-        emulate_attention_lo8(h, fa, ap, Rl, d.kv_heads, h->hd, st);
-        launch_attention(ap, B, h->hd, true, h->op_dt, st);
+        if (own) emulate_attention_lo8(h, fa, ap, Rl, d.kv_heads, h->hd, st);
+        if (ap.Ks) launch_attention_shared(ap, B, h->hd, h->op_dt, st);
+        else launch_attention(ap, B, h->hd, true, h->op_dt, st);
         if (!pruned) { decoder_tail(h, st, l, att, h->x, h->h, h->ff); continue; }
-        launch_gather_norm_rows(h->x, h->tstat, S, gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);      // (no weight: a plain row gather)
+        launch_gather_norm_rows(h->x, h->tstat, S, p.gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);      // (no weight: a plain row gather)
         decoder_tail(h, st, l, att, h->xg, h->hg, h->ffg);
         return true;
     }
     return false;
+}
+
+void alloc_decoder_ws(lr_engine* h, size_t Rl) {
+    const size_t D = h->d.hidden, ob = 2 * (size_t)(1 + h->created.prec);
+    auto W = [&](size_t bytes) { return h->dalloc(bytes, false); };
+    h->x = (float*)W(Rl * D * 4); h->h = W(Rl * D * ob); h->qkv = W(Rl * h->Nqkv * ob);
+    h->att = W(Rl * h->Hq * ob); h->ff = W(Rl * h->d.intermediate * ob); h->cs = (float*)W(Rl * h->hd * 4);
+    if (h->lora_k2max > 0) h->lt = W(Rl * (size_t)h->lora_k2max * ob);
+    h->pos_ids = (int*)W(Rl * 4); h->img_row = (int*)W(Rl * 4);
+}
+
+void push_decoder_weights(const lr_engine* h, std::vector<GemmWeight>& ws, size_t Rl) {
+    const int D = h->d.hidden, I = h->d.intermediate;
+    for (const DecLayer& L : h->dl) {
+        ws.push_back({L.qkv_w, h->Nqkv, D, Rl}); ws.push_back({L.o_w, D, h->Hq, Rl});
+        ws.push_back({L.gu_w, 2 * I, D, Rl}); ws.push_back({L.down_w, D, I, Rl});
+        if (L.lqkv.k2) {
+            ws.push_back({L.lqkv.A, L.lqkv.k2, D, Rl}); ws.push_back({L.lo.A, L.lo.k2, h->Hq, Rl});
+            ws.push_back({L.lgu.A, L.lgu.k2, D, Rl}); ws.push_back({L.ldown.A, L.ldown.k2, I, Rl});
+        }
+    }
 }
 
 void alloc_mean_pool(lr_engine* h, size_t rows, size_t vcap) {
@@ -289,117 +314,112 @@ void run_mean_pool_head(lr_engine* h, hipStream_t st, const int64_t* attention_m
     launch_reward_head(h->hL, nullptr, nullptr, 0.f, h->vh, d.value_head_dim, rewards_out, B, D, st);
 }
 
+// Host plan of one sample's image (h, w = hh, ww; its first crop NC and first image row SV): fills the sample's table entry and
+// returns its crop and image-row counts.  Phi-3-V: the HD crop grid, modeling_phi3_v.py:276-297.
+struct SamplePlan { int ncr, V; };
+static SamplePlan plan_hd_sample(const lr_engine* h, int64_t hh, int64_t ww, int NC, int SV, HdSample& smp, const char* who) {
+    const int img = h->d.clip_image, g2 = h->G / 2;
+    if (hh <= 0 || ww <= 0 || hh % img || ww % img) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive multiples of the crop size");
+    const int hc = (int)(hh / img), wc = (int)(ww / img);
+    smp = HdSample{hc, wc, NC, SV};
+    return {hc * wc + 1, hc * g2 * (wc * g2 + 1) + 1 + g2 * (g2 + 1)};
+}
+// LLaVA: anyres + unpad, modeling_llava_next.py:41-146,265-335
+static SamplePlan plan_llava_sample(const lr_engine* h, int64_t hh, int64_t ww, int NC, int SV, LlavaSample& smp, const char* who) {
+    const lr_model_desc& d = h->d;
+    if (hh <= 0 || ww <= 0) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive");
+    // transformers select_best_resolution: max effective resolution, then min waste
+    long best_eff = 0, best_waste = 0; int bh = 0, bw = 0;
+    for (int i = 0; i < d.n_pinpoints; ++i) {
+        const int ph = d.pinpoints[2 * i], pw = d.pinpoints[2 * i + 1];
+        const double sc = std::min((double)pw / (double)ww, (double)ph / (double)hh);
+        const long dw = (long)((double)ww * sc), dh = (long)((double)hh * sc);
+        const long eff = std::min(dw * dh, (long)(ww * hh)), waste = (long)pw * ph - eff;
+        if (eff > best_eff || (eff == best_eff && (bh == 0 || waste < best_waste))) { best_eff = eff; best_waste = waste; bh = ph; bw = pw; }
+    }
+    const int gh = bh / d.clip_image, gw = bw / d.clip_image, ch = gh * h->G, cw = gw * h->G;
+    int r0 = 0, r1 = ch, c0 = 0, c1 = cw;
+    // unpad_image (modeling_llava_next.py:109-146): new extent = int(round(x, 7)) -- 7 decimals, then truncation
+    auto trunc7 = [](double x) { return (int)(std::round(x * 1e7) / 1e7); };
+    if ((double)ww / (double)hh > (double)cw / (double)ch) {           // rows were padded
+        const int pad = (ch - trunc7((double)hh * ((double)cw / (double)ww))) / 2; r0 = pad; r1 = ch - pad;
+    } else {                                                           // columns were padded
+        const int pad = (cw - trunc7((double)ww * ((double)ch / (double)hh))) / 2; c0 = pad; c1 = cw - pad;
+    }
+    smp = LlavaSample{gh, gw, r0, r1, c0, c1, NC, SV};
+    return {1 + gh * gw, h->G * h->G + (r1 - r0) * (c1 - c0 + 1)};
+}
+
 // The image side of a pass, shared by lr_forward and lr_prefix_build: host plan (active crops, per-sample vision geometry, image-token
 // offsets) through the table ring, CLIP tower, HD transform / anyres packing and the projector; leaves the image rows in h->ev.
 struct VisionPlan { const int* d_voff; const int* voff; int SV, Vmax; };
 static VisionPlan run_vision(lr_engine* h, hipStream_t st, const void* pixel_values, int pix_dtype, const int64_t* image_sizes_host, int B,
                              int S, int n_crops, const char* who) {
-        const lr_model_desc& d = h->d;
-        const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, T = h->T, g2 = h->G / 2;
-        const int img = d.clip_image;
+    const lr_model_desc& d = h->d;
+    const int Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, T = h->T;
 
-        // ---- host plan: active crops, per-sample vision geometry, image-token offsets ----
-        // Phi-3-V: modeling_phi3_v.py:276-297 (HD crop grid);  LLaVA: modeling_llava_next.py:41-146,265-335 (anyres + unpad)
-        const int slot = h->slot_i; h->slot_i = (h->slot_i + 1) % lr_engine::NSLOT;
-        if (h->tab_used[slot]) LR_HIP_CHECK(hipEventSynchronize(h->tab_ev[slot]));   // bounds host run-ahead to NSLOT passes
-        char* th = h->tab_host + (size_t)slot * h->tab_bytes;
-        char* td = h->tab_dev + (size_t)slot * h->tab_bytes;
-        const size_t NCcap = (size_t)d.max_batch * d.max_crops;
-        const size_t smp_off = NCcap * 4, voff_off = smp_off + (size_t)d.max_batch * sizeof(LlavaSample);
-        int* crop_src = (int*)th;
-        HdSample* smp = (HdSample*)(th + smp_off);
-        LlavaSample* lsmp = (LlavaSample*)(th + smp_off);
-        int* voff = (int*)(th + voff_off);
-        int NC = 0, SV = 0, Vmax = 0;
-        for (int b = 0; b < B; ++b) {
-            const int64_t hh = image_sizes_host[2 * b], ww = image_sizes_host[2 * b + 1];
-            int ncr, V;
-            if (h->llava) {
-                if (hh <= 0 || ww <= 0) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive");
-                // transformers select_best_resolution: max effective resolution, then min waste
-                long best_eff = 0, best_waste = 0; int bh = 0, bw = 0;
-                for (int i = 0; i < d.n_pinpoints; ++i) {
-                    const int ph = d.pinpoints[2 * i], pw = d.pinpoints[2 * i + 1];
-                    const double sc = std::min((double)pw / (double)ww, (double)ph / (double)hh);
-                    const long dw = (long)((double)ww * sc), dh = (long)((double)hh * sc);
-                    const long eff = std::min(dw * dh, (long)(ww * hh)), waste = (long)pw * ph - eff;
-                    if (eff > best_eff || (eff == best_eff && (bh == 0 || waste < best_waste))) { best_eff = eff; best_waste = waste; bh = ph; bw = pw; }
-                }
-                const int gh = bh / img, gw = bw / img, ch = gh * h->G, cw = gw * h->G;
-                int r0 = 0, r1 = ch, c0 = 0, c1 = cw;
-                // unpad_image (modeling_llava_next.py:109-146): new extent = int(round(x, 7)) -- 7 decimals, then truncation
-                auto trunc7 = [](double x) { return (int)(std::round(x * 1e7) / 1e7); };
-                if ((double)ww / (double)hh > (double)cw / (double)ch) {           // rows were padded
-                    const int pad = (ch - trunc7((double)hh * ((double)cw / (double)ww))) / 2; r0 = pad; r1 = ch - pad;
-                } else {                                                           // columns were padded
-                    const int pad = (cw - trunc7((double)ww * ((double)ch / (double)hh))) / 2; c0 = pad; c1 = cw - pad;
-                }
-                ncr = 1 + gh * gw;
-                V = h->G * h->G + (r1 - r0) * (c1 - c0 + 1);
-                lsmp[b] = LlavaSample{gh, gw, r0, r1, c0, c1, NC, SV};
-            } else {
-                if (hh <= 0 || ww <= 0 || hh % img || ww % img) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive multiples of the crop size");
-                const int hc = (int)(hh / img), wc = (int)(ww / img);
-                ncr = hc * wc + 1;
-                smp[b] = HdSample{hc, wc, NC, SV};
-                V = hc * g2 * (wc * g2 + 1) + 1 + g2 * (g2 + 1);
-            }
-            if (ncr > n_crops) throw std::invalid_argument(std::string(who) + ": image_sizes needs more crops than pixel_values holds");
-            voff[b] = SV;
-            for (int c = 0; c < ncr; ++c) crop_src[NC++] = b * n_crops + c;
-            SV += V;
-            Vmax = V > Vmax ? V : Vmax;
-        }
-        voff[B] = SV;
-        LR_HIP_CHECK(hipMemcpyAsync(td, th, h->tab_bytes, hipMemcpyHostToDevice, st));
-        LR_HIP_CHECK(hipEventRecord(h->tab_ev[slot], st));
-        h->tab_used[slot] = true;
-        const int* d_crop_src = (const int*)td;
-        const HdSample* d_smp = (const HdSample*)(td + smp_off);
-        const LlavaSample* d_lsmp = (const LlavaSample*)(td + smp_off);
-        const int* d_voff = (const int*)(td + voff_off);
-        h->lastB = B; h->lastS = S; h->lastNC = NC; h->lastSV = SV; h->lastVmax = Vmax;
-        h->last_voff.assign(voff, voff + B + 1);
+    // ---- host plan: active crops, per-sample vision geometry, image-token offsets ----
+    const TableSlot tab(h);
+    char *th = tab.host(), *td = tab.dev();
+    const size_t smp_off = (size_t)d.max_batch * d.max_crops * 4, voff_off = smp_off + (size_t)d.max_batch * sizeof(LlavaSample);
+    int* crop_src = (int*)th;
+    int* voff = (int*)(th + voff_off);
+    int NC = 0, SV = 0, Vmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t hh = image_sizes_host[2 * b], ww = image_sizes_host[2 * b + 1];
+        const SamplePlan sp = h->llava ? plan_llava_sample(h, hh, ww, NC, SV, ((LlavaSample*)(th + smp_off))[b], who)
+                                       : plan_hd_sample(h, hh, ww, NC, SV, ((HdSample*)(th + smp_off))[b], who);
+        if (sp.ncr > n_crops) throw std::invalid_argument(std::string(who) + ": image_sizes needs more crops than pixel_values holds");
+        voff[b] = SV;
+        for (int c = 0; c < sp.ncr; ++c) crop_src[NC++] = b * n_crops + c;
+        SV += sp.V;
+        Vmax = std::max(Vmax, sp.V);
+    }
+    voff[B] = SV;
+    tab.commit(st);
+    const int* d_crop_src = (const int*)td;
+    const int* d_voff = (const int*)(td + voff_off);
+    h->lastB = B; h->lastS = S; h->lastNC = NC; h->lastSV = SV; h->lastVmax = Vmax;
+    h->last_voff.assign(voff, voff + B + 1);
 
-        // ---- CLIP tower (utils/utils.py:266-273) ----
-        const int Rp = NC * (T - 1), Rc = NC * T;
-        const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision stage's operand form (covers the projector)
-        launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, img, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, fv.prec);
-        Operand pa = operand16(h->patchA, h->Kpad, Rp, fv);
-        linear(h, st, fv, Linear{h->patch_w, nullptr, Hc, h->Kpad, EPI_OUT_F32, ACT_NONE}, pa, h->patch_out);
-        launch_clip_embed(h->patch_out, h->cls, h->pos, h->pre_w, h->pre_b, h->clip_x, NC, T, Hc, d.clip_ln_eps, st);
-        const int ncl = h->lim_clip >= 0 && h->lim_clip < d.clip_layers ? h->lim_clip : d.clip_layers;
-        for (int l = 0; l < ncl; ++l) {
-            const ClipLayer& c = h->cl[l];
-            const Linear qkv{c.qkv_w, c.qkv_b, 3 * Hc, Hc, EPI_OUT_OP, ACT_NONE}, out{c.out_w, c.out_b, Hc, Hc, EPI_RESADD_F32, ACT_NONE},
-                         fc1{c.fc1_w, c.fc1_b, Mc, Hc, EPI_OUT_OP, ACT_QUICK_GELU}, fc2{c.fc2_w, c.fc2_b, Hc, Mc, EPI_RESADD_F32, ACT_NONE};
-            Operand n = norm_rows(h, st, fv, &qkv, h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
-            const Operand q = linear(h, st, fv, qkv, n, h->clip_qkv);
-            AttnParams ap{h->clip_qkv, h->clip_qkv, h->clip_qkv, h->clip_att, nullptr, nullptr, 0, 3 * Hc, Hc, 0, Hc, 2 * Hc, T, d.clip_heads, 0.125f, 1};
-            Operand att = apply_prec(h, fv, ap, q, Rc);
-            emulate_attention_lo8(h, fv, ap, Rc, d.clip_heads, 64, st);
-            launch_attention(ap, NC, 64, false, h->op_dt, st);
-            linear(h, st, fv, out, att, h->clip_x);
-            n = norm_rows(h, st, fv, &fc1, h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
-            Operand ff = linear(h, st, fv, fc1, n, h->clip_ff, &fc2);
-            linear(h, st, fv, fc2, ff, h->clip_x);
-        }
-        const Linear p0{h->p0_w, h->p0_b, D, h->llava ? Hc : 4 * Hc, EPI_OUT_OP, ACT_GELU_ERF}, p2{h->p2_w, h->p2_b, D, D, EPI_OUT_F32, ACT_NONE};
-        if (h->llava) {
-            // ---- per-token projector, then anyres packing (modeling_llava_next.py get_image_features/pack_image_features) ----
-            launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, fv.prec);
-            Operand a = operand16(h->hdA, Hc, Rp, fv);
-            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
-            linear(h, st, fv, p2, p1, h->pf32);
-            launch_llava_pack(h->pf32, d_lsmp, B, SV, h->G, D, h->newline, h->ev, st);
-        } else {
-            // ---- HD transform + projector (modeling_phi3_v.py:254-303) ----
-            launch_hd_gather(h->clip_x, d_smp, B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, fv.prec);
-            Operand a = operand16(h->hdA, 4 * Hc, SV, fv);
-            Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
-            linear(h, st, fv, p2, p1, h->ev);
-        }
-        return VisionPlan{d_voff, voff, SV, Vmax};
+    // ---- CLIP tower (utils/utils.py:266-273) ----
+    const int Rp = NC * (T - 1), Rc = NC * T;
+    const Form fv = h->form(h->pm_clip);          // lr_set_precision_map: the vision stage's operand form (covers the projector)
+    launch_im2col(pixel_values, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, d_crop_src, NC, d.clip_image, d.clip_patch, h->Kpad, h->patchA, h->op_dt, st, fv.prec);
+    Operand pa = operand16(h->patchA, h->Kpad, Rp, fv);
+    linear(h, st, fv, Linear{h->patch_w, nullptr, Hc, h->Kpad, EPI_OUT_F32, ACT_NONE}, pa, h->patch_out);
+    launch_clip_embed(h->patch_out, h->cls, h->pos, h->pre_w, h->pre_b, h->clip_x, NC, T, Hc, d.clip_ln_eps, st);
+    for (int l = 0, ncl = h->n_tower_layers(d.clip_layers); l < ncl; ++l) {
+        const ClipLayer& c = h->cl[l];
+        const Linear qkv{c.qkv_w, c.qkv_b, 3 * Hc, Hc, EPI_OUT_OP, ACT_NONE}, out{c.out_w, c.out_b, Hc, Hc, EPI_RESADD_F32, ACT_NONE},
+                     fc1{c.fc1_w, c.fc1_b, Mc, Hc, EPI_OUT_OP, ACT_QUICK_GELU}, fc2{c.fc2_w, c.fc2_b, Hc, Mc, EPI_RESADD_F32, ACT_NONE};
+        Operand n = norm_rows(h, st, fv, &qkv, h->clip_x, c.ln1_w, c.ln1_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+        const Operand q = linear(h, st, fv, qkv, n, h->clip_qkv);
+        AttnParams ap{h->clip_qkv, h->clip_qkv, h->clip_qkv, h->clip_att, nullptr, nullptr, 0, 3 * Hc, Hc, 0, Hc, 2 * Hc, T, d.clip_heads, 0.125f, 1};
+        Operand att = apply_prec(h, fv, ap, q, Rc);
+        emulate_attention_lo8(h, fv, ap, Rc, d.clip_heads, 64, st);
+        launch_attention(ap, NC, 64, false, h->op_dt, st);
+        linear(h, st, fv, out, att, h->clip_x);
+        n = norm_rows(h, st, fv, &fc1, h->clip_x, c.ln2_w, c.ln2_b, h->clip_h, Rc, Hc, d.clip_ln_eps);
+        Operand ff = linear(h, st, fv, fc1, n, h->clip_ff, &fc2);
+        linear(h, st, fv, fc2, ff, h->clip_x);
+    }
+    const Linear p0{h->p0_w, h->p0_b, D, h->llava ? Hc : 4 * Hc, EPI_OUT_OP, ACT_GELU_ERF}, p2{h->p2_w, h->p2_b, D, D, EPI_OUT_F32, ACT_NONE};
+    if (h->llava) {
+        // ---- per-token projector, then anyres packing (modeling_llava_next.py get_image_features/pack_image_features) ----
+        launch_clip_tokens(h->clip_x, h->hdA, NC, T, Hc, h->op_dt, st, fv.prec);
+        Operand a = operand16(h->hdA, Hc, Rp, fv);
+        Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+        linear(h, st, fv, p2, p1, h->pf32);
+        launch_llava_pack(h->pf32, (const LlavaSample*)(td + smp_off), B, SV, h->G, D, h->newline, h->ev, st);
+    } else {
+        // ---- HD transform + projector (modeling_phi3_v.py:254-303) ----
+        launch_hd_gather(h->clip_x, (const HdSample*)(td + smp_off), B, SV, T, Hc, h->sub_gn, h->glb_gn, h->hdA, h->op_dt, st, fv.prec);
+        Operand a = operand16(h->hdA, 4 * Hc, SV, fv);
+        Operand p1 = linear(h, st, fv, p0, a, h->proj1, &p2);
+        linear(h, st, fv, p2, p1, h->ev);
+    }
+    return VisionPlan{d_voff, voff, SV, Vmax};
 }
 
 // Tail of a pass (rw_model:376-448): final norm of the row each reward is read from, SkipCA over the image rows in `ev`, value head.
@@ -425,15 +445,11 @@ static void reward_tail(lr_engine* h, hipStream_t st, int flags, int S, const fl
     launch_slot_check(h->tstat, d_voff, rewards_out, B, d.value_head_dim, st, voff_stride);
 }
 
-// ---- shared image prefix: layout of a cache and the signature of everything its bits depend on ----
-// [256-byte head: int {0, V, image slots among the shared tokens} | per decoder layer l < nl: the qkv rows of the n_shared shared
-//  positions exactly as that layer's attention site reads them (post-RoPE, [hi | lo] where the site's form is split; the row stride of
-//  the qkv buffer, so the attention kernel's per-thread offsets serve both sources) | ev: V projected image rows, fp32]
-struct PrefixLayout { std::vector<size_t> layer; size_t ev = 0, total = 0; int nl = 0; };
+// ---- shared image prefix: the layout of a cache (PrefixLayout, engine.h) and the signature of everything its bits depend on ----
 static PrefixLayout prefix_layout(const lr_engine* h, int n_shared, int V) {
     PrefixLayout L;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    L.nl = h->lim_layers >= 0 && h->lim_layers < h->d.layers ? h->lim_layers : h->d.layers;
+    L.nl = h->n_layers();
     size_t off = 256;
     for (int l = 0; l < L.nl; ++l) {
         L.layer.push_back(off);
@@ -481,7 +497,7 @@ int lr_create(const lr_model_desc* desc, int device, lr_handle* out) {
         e = new lr_engine();
         e->d = *desc;
         e->device = device;
-        e->op_dt = desc->operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16;
+        e->op_dt = op_dtype(desc->operand_dtype);
         e->created = Form{desc->precise ? 1 : 0, desc->precise == 2 ? 1 : 0};
         e->sched_mem = (int*)e->dalloc(64, true);
         e->w8a8 = desc->w8a8 ? 1 : 0;
@@ -567,7 +583,7 @@ int lr_upload_weight(lr_handle h, const char* name, const void* data, const int6
         }
         const float* f32 = (const float*)dev_src;
         if (dtype != LR_DT_F32) {
-            launch_cvt_to_f32(dev_src, dtype == LR_DT_F16 ? DT_F16 : DT_BF16, h->stage_f32, n, 0);
+            launch_cvt_to_f32(dev_src, op_dtype(dtype), h->stage_f32, n, 0);
             f32 = h->stage_f32;
         }
         if (s.wid >= 0 && s.lo_dst) {          // split-operand mode: this tensor's buffer has a residual twin
@@ -641,7 +657,7 @@ int lr_finalize(lr_handle h) {
         if (h->qwen) { finalize_qwen(h); h->finalized = true; return; }
         const lr_model_desc& d = h->d;
         const size_t B = d.max_batch, S = d.max_seq, C = d.max_crops;
-        const size_t Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden, I = d.intermediate;
+        const size_t Hc = d.clip_hidden, Mc = d.clip_mlp, D = d.hidden;
         const size_t PAD = 256;
         const size_t NC = B * C, Rc = NC * h->T + PAD, Rp = NC * (h->T - 1) + PAD, SV = B * (size_t)h->Vcap + PAD, Rl = B * S + PAD;
         auto W = [&](size_t bytes) { return h->dalloc(bytes, false); };
@@ -655,10 +671,8 @@ int lr_finalize(lr_handle h) {
             h->hdA = W(SV * 4 * Hc * ob); h->proj1 = W(SV * D * ob);
         }
         h->ev = (float*)W(SV * D * 4);
-        h->x = (float*)W(Rl * D * 4); h->h = W(Rl * D * ob); h->qkv = W(Rl * h->Nqkv * ob);
-        h->att = W(Rl * h->Hq * ob); h->ff = W(Rl * I * ob); h->cs = (float*)W(Rl * h->hd * 4);
-        if (h->lora_k2max > 0) h->lt = W(Rl * (size_t)h->lora_k2max * ob);
-        h->pos_ids = (int*)W(Rl * 4); h->img_row = (int*)W(Rl * 4); h->tstat = (int*)W(B * 16);
+        alloc_decoder_ws(h, Rl);
+        h->tstat = (int*)W(B * 16);
         h->hL = (float*)W(B * D * 4); h->tq = (float*)W(B * D * 4); h->tkq = (float*)W(B * D * 4);
         h->tsc = (float*)W(B * (size_t)h->Vcap * 4); h->tctx = (float*)W(B * D * 4); h->tao = (float*)W(B * D * 4);
         if (d.mean_hidden_state) alloc_mean_pool(h, Rl, (size_t)h->Vcap);
@@ -678,14 +692,7 @@ int lr_finalize(lr_handle h) {
             }
             if (h->llava) { ws.push_back({h->p0_w, (int)D, (int)Hc, Rp}); ws.push_back({h->p2_w, (int)D, (int)D, Rp}); }
             else { ws.push_back({h->p0_w, (int)D, (int)(4 * Hc), SV}); ws.push_back({h->p2_w, (int)D, (int)D, SV}); }
-            for (const DecLayer& L : h->dl) {
-                ws.push_back({L.qkv_w, h->Nqkv, (int)D, Rl}); ws.push_back({L.o_w, (int)D, h->Hq, Rl});
-                ws.push_back({L.gu_w, (int)(2 * I), (int)D, Rl}); ws.push_back({L.down_w, (int)D, (int)I, Rl});
-                if (L.lqkv.k2) {
-                    ws.push_back({L.lqkv.A, L.lqkv.k2, (int)D, Rl}); ws.push_back({L.lo.A, L.lo.k2, h->Hq, Rl});
-                    ws.push_back({L.lgu.A, L.lgu.k2, (int)D, Rl}); ws.push_back({L.ldown.A, L.ldown.k2, (int)I, Rl});
-                }
-            }
+            push_decoder_weights(h, ws, Rl);
             prepare_twins(h, ws);
         }
         h->finalized = true;
@@ -743,10 +750,7 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
         if (!input_ids || !attention_mask || !pixel_values || !image_sizes_host || !rewards_out)
             throw std::invalid_argument("lr_forward: null argument (every row must carry an image, modeling_phi3_v.py:252)");
         const lr_model_desc& d = h->d;
-        if (B < 1 || B > d.max_batch) throw std::invalid_argument("lr_forward: batch exceeds max_batch");
-        if (S < 1 || S > d.max_seq) throw std::invalid_argument("lr_forward: sequence exceeds max_seq");
-        if (n_crops < 2 || n_crops > d.max_crops) throw std::invalid_argument("lr_forward: n_crops exceeds max_crops");
-        if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_forward: pixel dtype must be F32 or BF16");
+        check_batch(h, B, "lr_forward"); check_seq(h, S, "lr_forward"); check_crops(h, n_crops, "lr_forward"); check_pix_dtype(pix_dtype, "lr_forward");
         hipStream_t st = (hipStream_t)hip_stream;
         const int D = d.hidden;
         const VisionPlan vp = run_vision(h, st, pixel_values, pix_dtype, image_sizes_host, B, S, n_crops, "lr_forward");
@@ -760,7 +764,7 @@ int lr_forward(lr_handle h, const int64_t* input_ids, const int64_t* attention_m
                           S + (d.rope_flash_convention ? 1 : 0));      // seq_len the rotary module is called with (lr_model_desc.rope_flash_convention)
         const int last_pos = (flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0;
         const int gather = (d.mean_hidden_state || (flags & LR_FWD_KEEP_HIDDEN_STATES)) ? 0 : 1 + last_pos;
-        h->last_pruned = run_decoder_stack(h, st, attention_mask, B, S, gather);
+        h->last_pruned = run_decoder_stack(h, st, DecoderPass{attention_mask, B, S, gather});
         if (d.mean_hidden_state) {      // rw_model:398-406: SkipCA + norm on every token, masked mean, value head
             run_mean_pool_head(h, st, attention_mask, B, S, voff, Vmax, nullptr, !(flags & LR_FWD_NO_FINAL_NORM), rewards_out);
             launch_slot_check(h->tstat, d_voff, rewards_out, B, d.value_head_dim, st);
@@ -789,8 +793,7 @@ int lr_prefix_build(lr_handle h, const int64_t* prefix_ids, int n_prefix, const 
         if (total_len <= 0) total_len = n_prefix;
         if (NS < 64) throw std::invalid_argument("lr_prefix_build: the prefix holds no whole 64-key tile (n_shared == 0): score such rows with lr_forward");
         if (total_len < n_prefix || total_len > d.max_seq) throw std::invalid_argument("lr_prefix_build: total_len must lie in [n_prefix, max_seq]");
-        if (n_crops < 2 || n_crops > d.max_crops) throw std::invalid_argument("lr_prefix_build: n_crops exceeds max_crops");
-        if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_prefix_build: pixel dtype must be F32 or BF16");
+        check_crops(h, n_crops, "lr_prefix_build"); check_pix_dtype(pix_dtype, "lr_prefix_build");
         if (((uintptr_t)cache) & 255) throw std::invalid_argument("lr_prefix_build: the cache must be 256-byte aligned");
         hipStream_t st = (hipStream_t)hip_stream;
         const int D = d.hidden;
@@ -805,22 +808,9 @@ int lr_prefix_build(lr_handle h, const int64_t* prefix_ids, int n_prefix, const 
         launch_embed(prefix_ids, h->img_row, h->wte, h->ev, h->x, NS, D, d.vocab_size, st);
         const int rot = total_len + (d.rope_flash_convention ? 1 : 0);       // what lr_forward passes for a batch of that width
         launch_rope_table(h->pos_ids, h->tstat, 1, NS, h->inv_s, h->inv_l, d.rope_scaling, d.orig_max_pos, h->half, h->cs, st, rot);
-        const float ascale = 1.0f / std::sqrt((float)h->hd);
-        const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
-        for (int l = 0; l < L.nl; ++l) {
-            const DecLayer& Ly = h->dl[l];
-            const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
-            const Linear qkv{Ly.qkv_w, Ly.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &Ly.lqkv, h->cs, Hq + Hkv, h->hd};
-            void* rows = base + L.layer[l];                 // the projection writes its rows straight into the cache
-            Operand n = norm_rows(h, st, fq, &qkv, h->x, Ly.ln1, nullptr, h->h, NS, D, d.rms_eps);
-            const Operand q = qkv_rope(h, st, fq, qkv, n, rows, h->qkv32, (size_t)d.max_batch * d.max_seq);
-            check_layout(q, fa, "attention");
-            if (l == L.nl - 1) break;                       // the last layer contributes K and V only
-            AttnParams ap{rows, rows, rows, h->att, nullptr, nullptr, 0, Nqkv, Hq, 0, Hq, Hq + Hkv, NS, d.heads, ascale, d.heads / d.kv_heads};
-            const Operand att = apply_prec(h, fa, ap, q, NS);
-            launch_attention(ap, 1, h->hd, true, h->op_dt, st);
-            decoder_tail(h, st, l, att, h->x, h->h, h->ff);
-        }
+        DecoderPass pass{nullptr, 1, NS, 0, &L};
+        pass.kv_out = base;                                 // every layer's qkv rows land in the cache; the last layer stops there
+        run_decoder_stack(h, st, pass);
         LR_HIP_CHECK(hipMemcpyAsync(base + L.ev, h->ev, (size_t)V * D * 4, hipMemcpyDeviceToDevice, st));
         LR_HIP_CHECK(hipGetLastError());
         h->lastB = 0; h->last_pruned = false;               // (no reward rows: the taps of a forward have nothing to show)
@@ -851,7 +841,7 @@ int lr_forward_prefixed(lr_handle h, const void* cache, const lr_prefix_info* in
         if (info->form_signature != prefix_signature(h) || info->n_layers != L.nl || info->cache_bytes != L.total)
             throw std::logic_error("lr_forward_prefixed: stale prefix cache: the operand forms (precision map / sites), layer limits or kernel settings "
                                    "changed since it was built; build it again");
-        if (B < 1 || B > d.max_batch) throw std::invalid_argument("lr_forward_prefixed: batch exceeds max_batch");
+        check_batch(h, B, "lr_forward_prefixed");
         if (T < 1 || NS + T > d.max_seq) throw std::invalid_argument("lr_forward_prefixed: n_shared + T exceeds max_seq");
         const int S = NS + T, rot = S + (d.rope_flash_convention ? 1 : 0);
         if ((rot > d.orig_max_pos ? 1 : 0) != info->long_factors)
@@ -866,28 +856,9 @@ int lr_forward_prefixed(lr_handle h, const void* cache, const lr_prefix_info* in
         launch_token_plan(input_ids, attention_mask, B, T, hdr, h->img_row, h->pos_ids, h->tstat, st, -1L, 0, NS, hdr + 2, 0);
         launch_embed(input_ids, h->img_row, h->wte, ev, h->x, Rl, D, d.vocab_size, st);
         launch_rope_table(h->pos_ids, h->tstat, B, T, h->inv_s, h->inv_l, d.rope_scaling, d.orig_max_pos, h->half, h->cs, st, rot);
-        const int last_pos = (flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0, gather = 1 + last_pos;
-        const float ascale = 1.0f / std::sqrt((float)h->hd);
-        const int Hq = h->Hq, Hkv = h->Hkv, Nqkv = h->Nqkv;
-        h->last_pruned = false;
-        for (int l = 0; l < L.nl; ++l) {
-            const DecLayer& Ly = h->dl[l];
-            const Form fq = h->site(l, lr_engine::SITE_QKV), fa = h->site(l, lr_engine::SITE_ATTN);
-            const Linear qkv{Ly.qkv_w, Ly.qkv_b, Nqkv, D, EPI_ROPE_OP, ACT_NONE, &Ly.lqkv, h->cs, Hq + Hkv, h->hd};
-            Operand n = norm_rows(h, st, fq, &qkv, h->x, Ly.ln1, nullptr, h->h, Rl, D, d.rms_eps);
-            const Operand q = qkv_rope(h, st, fq, qkv, n, h->qkv, h->qkv32, (size_t)d.max_batch * d.max_seq);
-            AttnParams ap{h->qkv, h->qkv, h->qkv, h->att, attention_mask, nullptr, 0, Nqkv, Hq, 0, Hq, Hq + Hkv, T, d.heads, ascale, d.heads / d.kv_heads};
-            ap.Ks = ap.Vs = base + L.layer[l];
-            ap.n_shared = NS;
-            const bool pruned = l == L.nl - 1;              // the last layer runs for the row each reward is read from only (run_decoder_stack)
-            if (pruned) { ap.O = h->attg; ap.qsel = h->tstat; ap.qsel_stride = 4; ap.qsel_last = gather == 2 ? 1 : 0; }
-            const Operand att = apply_prec(h, fa, ap, q, pruned ? B : Rl);
-            launch_attention_shared(ap, B, h->hd, h->op_dt, st);
-            if (!pruned) { decoder_tail(h, st, l, att, h->x, h->h, h->ff); continue; }
-            launch_gather_norm_rows(h->x, h->tstat, T, gather == 2 ? 1 : 0, nullptr, 0.f, h->xg, B, D, st);
-            decoder_tail(h, st, l, att, h->xg, h->hg, h->ffg);
-            h->last_pruned = true;
-        }
+        DecoderPass pass{attention_mask, B, T, 1 + ((flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0), &L};
+        pass.kv_shared = base; pass.n_shared = NS;          // the cached rows in front of every row's own keys; the last layer gathered
+        h->last_pruned = run_decoder_stack(h, st, pass);
         h->lastB = 0;                                       // (the taps of a forward describe whole rows; there are none here)
         reward_tail(h, st, flags, T, ev, hdr, 0, V, B, rewards_out);
         LR_HIP_CHECK(hipGetLastError());
@@ -970,7 +941,7 @@ int lr_op_gemm_bt(const void* A, const void* W, void* C, const float* bias, int 
                   int epi, int act, int operand_dtype, int tile, void* hip_stream) {
     return op_guard([&] {
         GemmParams p{A, W, C, bias, M, N, K, lda, ldw, ldc, epi, act, nullptr, 0, 0};
-        launch_gemm_bt(p, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, tile, (hipStream_t)hip_stream);
+        launch_gemm_bt(p, op_dtype(operand_dtype), tile, (hipStream_t)hip_stream);
     });
 }
 
@@ -980,7 +951,7 @@ int lr_op_gemm_bt_split(const void* A, const void* W, void* C, const float* bias
         const int nout = epi == EPI_SWIGLU_OP ? N / 2 : N;
         const bool op_out = epi == EPI_OUT_OP || epi == EPI_SWIGLU_OP;
         GemmParams p{A, W, C, bias, M, N, 2 * K, 2 * K, K, op_out ? 2 * nout : nout, epi, act, nullptr, 0, 0, K, op_out ? nout : 0};
-        launch_gemm_bt(p, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, tile, (hipStream_t)hip_stream);
+        launch_gemm_bt(p, op_dtype(operand_dtype), tile, (hipStream_t)hip_stream);
     });
 }
 
@@ -992,7 +963,7 @@ int lr_op_gemm_bt_ext(const void* A, const void* W, const void* T, const void* B
         GemmParams p{A, W, C, bias, M, N, K, K, K, nout, epi, act, nullptr, 0, 0};
         if (split) { p.K = 2 * K; p.lda = 2 * K; p.kw = K; if (op_out) { p.ldc = 2 * nout; p.split = nout; } }
         p.A2 = T; p.lda2 = (split ? 2 : 1) * k2; p.W2 = Bm; p.W2lo = Blo; p.ldw2 = k2; p.k2 = k2;
-        launch_gemm_bt(p, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, 6, (hipStream_t)hip_stream);
+        launch_gemm_bt(p, op_dtype(operand_dtype), 6, (hipStream_t)hip_stream);
     });
 }
 
@@ -1001,7 +972,7 @@ size_t lr_op_lo8_scratch_bytes(int M, int K) { return ((lo8_scale_bytes(M, K) + 
 int lr_op_gemm_bt_mixed(void* A, const void* W, void* W8, void* scratch, void* C, const float* bias, int M, int N, int K, int epi, int act,
                         int operand_dtype, int flags, int* wexp, void* hip_stream) {
     return op_guard([&] {
-        const int dt = operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16;
+        const int dt = op_dtype(operand_dtype);
         hipStream_t st = (hipStream_t)hip_stream;
         if (!wexp || !scratch || K % 128) throw std::runtime_error("lr_op_gemm_bt_mixed: wexp and scratch are required, K % 128 == 0");
         unsigned char* scales = (unsigned char*)scratch;                                                    // lr_op_lo8_scratch_bytes(M, K)
@@ -1055,7 +1026,7 @@ int lr_op_gemm_bt_fp6ab(const void* A, const void* W, const void* W6, const void
 
 int lr_op_quantize_rows_fp8(const void* x, int rows, int K, int ldx, void* q, float* scale, int operand_dtype, void* hip_stream) {
     return op_guard([&] {
-        launch_quantize_rows_fp8(x, ldx, K, rows, q, K, scale, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_quantize_rows_fp8(x, ldx, K, rows, q, K, scale, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1064,7 +1035,7 @@ int lr_op_gemm_fp8(const void* A8, const float* ascale, const void* W8, const fl
     return op_guard([&] {
         GemmParams p{A8, W8, C, bias, M, N, K, K, K, ldc, epi, act, nullptr, 0, 0};
         p.ascale = ascale; p.wscale = wscale;
-        launch_gemm_bt8_fp8(p, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_gemm_bt8_fp8(p, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1072,7 +1043,7 @@ int lr_op_gemm_rope(const void* A, const void* W, void* C, const float* bias, co
                     int rope_hd, int operand_dtype, int tile, void* hip_stream) {
     return op_guard([&] {
         GemmParams p{A, W, C, bias, M, N, K, K, K, N, EPI_ROPE_OP, ACT_NONE, cs, rope_cols, rope_hd};
-        launch_gemm_bt(p, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, tile, (hipStream_t)hip_stream);
+        launch_gemm_bt(p, op_dtype(operand_dtype), tile, (hipStream_t)hip_stream);
     });
 }
 
@@ -1081,7 +1052,7 @@ int lr_op_attention(const void* Q, const void* K, const void* V, void* O, const 
                     int operand_dtype, void* hip_stream) {
     return op_guard([&] {
         AttnParams p{Q, K, V, O, mask, kmin, 1, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group};
-        launch_attention(p, batch, head_dim, causal != 0, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_attention(p, batch, head_dim, causal != 0, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1091,7 +1062,7 @@ int lr_op_attention_split(const void* Q, const void* K, const void* V, void* O, 
     return op_guard([&] {
         AttnParams p{Q, K, V, O, mask, kmin, 1, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group, nullptr, 0, lo_off, o_split};
         p.lazy_t = ATT_LAZY_T_DEFAULT;
-        launch_attention(p, batch, head_dim, causal != 0, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_attention(p, batch, head_dim, causal != 0, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1101,7 +1072,7 @@ int lr_op_attention_split_ex(const void* Q, const void* K, const void* V, void* 
     return op_guard([&] {
         AttnParams p{Q, K, V, O, mask, kmin, 1, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group, nullptr, 0, lo_off, o_split};
         p.lazy_t = lazy_threshold;
-        launch_attention(p, batch, head_dim, causal != 0, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_attention(p, batch, head_dim, causal != 0, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1112,7 +1083,7 @@ int lr_op_attention_shared(const void* Q, const void* K, const void* V, const vo
         AttnParams p{Q, K, V, O, mask, nullptr, 0, ldq, ldo, qoff, koff, voff, S, heads, scale, kv_group, nullptr, 0, lo_off, o_split};
         p.lazy_t = lazy_threshold;
         p.Ks = Ks; p.Vs = Vs; p.n_shared = n_shared;
-        launch_attention_shared(p, batch, head_dim, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream);
+        launch_attention_shared(p, batch, head_dim, op_dtype(operand_dtype), (hipStream_t)hip_stream);
     });
 }
 
@@ -1132,7 +1103,7 @@ static void attention_segments(AttnParams p, const int32_t* cu, int n_seg, int h
     LR_HIP_CHECK(hipMalloc((void**)&d_items, items.size() * sizeof(int4)));
     LR_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice, st));
     p.S = max_len; p.kv_group = 1; p.items = d_items; p.n_items = (int)items.size();
-    try { launch_attention(p, 1, head_dim, false, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, st); }
+    try { launch_attention(p, 1, head_dim, false, op_dtype(operand_dtype), st); }
     catch (...) { hipStreamSynchronize(st); hipFree(d_items); throw; }
     LR_HIP_CHECK(hipStreamSynchronize(st));
     LR_HIP_CHECK(hipFree(d_items));
@@ -1159,7 +1130,7 @@ int lr_op_attention_segments_split(const void* Q, const void* K, const void* V, 
 
 int lr_op_norm_rows(const float* x, const float* w, const float* b, void* y, int rows, int H, float eps, int operand_dtype,
                     void* hip_stream) {
-    return op_guard([&] { launch_norm_rows(x, w, b, y, rows, H, eps, operand_dtype == LR_DT_F16 ? DT_F16 : DT_BF16, (hipStream_t)hip_stream); });
+    return op_guard([&] { launch_norm_rows(x, w, b, y, rows, H, eps, op_dtype(operand_dtype), (hipStream_t)hip_stream); });
 }
 
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std_, float offset, int bf16_round,

@@ -176,7 +176,7 @@ void build_weight_table_qwen(lr_engine* e) {
 
 void finalize_qwen(lr_engine* h) {
     const lr_model_desc& d = h->d;
-    const size_t B = d.max_batch, S = d.max_seq, P = d.max_patches, D = d.hidden, I = d.intermediate;
+    const size_t B = d.max_batch, S = d.max_seq, P = d.max_patches, D = d.hidden;
     const size_t PAD = 256, Rv = P + PAD, Rm = P / h->vunit + PAD, Rl = B * S + PAD;
     auto W = [&](size_t bytes) { return h->dalloc(bytes, false); };
     const size_t ob = 2 * (size_t)(1 + h->created.prec);      // bytes per operand element (hi [+ lo])
@@ -184,10 +184,8 @@ void finalize_qwen(lr_engine* h) {
     h->vqkv = W(Rv * 3 * h->vHp * ob); h->vatt = W(Rv * h->vHp * ob);
     h->vff = W(Rv * h->vIp * ob); h->vcs = (float*)W(Rv * h->vhdp * 4); h->vm1 = W(Rm * h->vHm * ob);
     h->ev = (float*)W(Rm * D * 4);
-    h->x = (float*)W(Rl * D * 4); h->h = W(Rl * D * ob); h->qkv = W(Rl * h->Nqkv * ob);
-    h->att = W(Rl * h->Hq * ob); h->ff = W(Rl * I * ob); h->cs = (float*)W(Rl * h->hd * 4);
-    if (h->lora_k2max > 0) h->lt = W(Rl * (size_t)h->lora_k2max * ob);
-    h->pos_ids = (int*)W(Rl * 4); h->img_row = (int*)W(Rl * 4); h->pos3 = (int*)W(3 * Rl * 4);
+    alloc_decoder_ws(h, Rl);
+    h->pos3 = (int*)W(3 * Rl * 4);
     h->tstat = (int*)W(B * 16); h->rstat = (int*)W(B * 16);
     h->hL = (float*)W(B * D * 4); h->tao = (float*)W(B * D * 4);
     if (d.mean_hidden_state) alloc_mean_pool(h, Rl, 0);
@@ -205,14 +203,7 @@ void finalize_qwen(lr_engine* h) {
             ws.push_back({L.gu_w, 2 * vIp, vH, Rv}); ws.push_back({L.down_w, vH, vIp, Rv});
         }
         ws.push_back({h->m0_w, vHm, vHm, Rm}); ws.push_back({h->m2_w, (int)D, vHm, Rm});
-        for (const DecLayer& L : h->dl) {
-            ws.push_back({L.qkv_w, h->Nqkv, (int)D, Rl}); ws.push_back({L.o_w, (int)D, h->Hq, Rl});
-            ws.push_back({L.gu_w, (int)(2 * I), (int)D, Rl}); ws.push_back({L.down_w, (int)D, (int)I, Rl});
-            if (L.lqkv.k2) {
-                ws.push_back({L.lqkv.A, L.lqkv.k2, (int)D, Rl}); ws.push_back({L.lo.A, L.lo.k2, h->Hq, Rl});
-                ws.push_back({L.lgu.A, L.lgu.k2, (int)D, Rl}); ws.push_back({L.ldown.A, L.ldown.k2, (int)I, Rl});
-            }
-        }
+        push_decoder_weights(h, ws, Rl);
         prepare_twins(h, ws);
     }
     LR_HIP_CHECK(hipMemset(h->tstat, 0, B * 16));
@@ -245,20 +236,17 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         if (!input_ids || !attention_mask || !pixel_values || !grid_thw || !rewards_out)
             throw std::invalid_argument("lr_forward_qwen: null argument (inputs_batch needs input_ids, attention_mask, pixel_values, image_grid_thw)");
         const lr_model_desc& d = h->d;
-        if (B < 1 || B > d.max_batch) throw std::invalid_argument("lr_forward_qwen: batch exceeds max_batch");
-        if (S < 1 || S > d.max_seq) throw std::invalid_argument("lr_forward_qwen: sequence exceeds max_seq");
+        check_batch(h, B, "lr_forward_qwen"); check_seq(h, S, "lr_forward_qwen");
         if (n_images < 1 || n_images > LR_QWEN_IMAGES_PER_ROW * d.max_batch)
             throw std::invalid_argument("lr_forward_qwen: n_images must be in [1, 4 * max_batch]");
-        if (pix_dtype != LR_DT_F32 && pix_dtype != LR_DT_BF16) throw std::invalid_argument("lr_forward_qwen: pixel dtype must be F32 or BF16");
+        check_pix_dtype(pix_dtype, "lr_forward_qwen");
         hipStream_t st = (hipStream_t)hip_stream;
         const int D = d.hidden, m = d.vit_merge, unit = h->vunit;
         const int vH = h->vH, vHp = h->vHp, vhdp = h->vhdp, vIp = h->vIp, vHm = h->vHm;
 
         // ---- host plan (transformers.vision_utils get_vision_window_index / get_vision_position_ids / cu_seqlens) ----
-        const int slot = h->slot_i; h->slot_i = (h->slot_i + 1) % lr_engine::NSLOT;
-        if (h->tab_used[slot]) LR_HIP_CHECK(hipEventSynchronize(h->tab_ev[slot]));
-        char* th = h->tab_host + (size_t)slot * h->tab_bytes;
-        char* td = h->tab_dev + (size_t)slot * h->tab_bytes;
+        const TableSlot tab(h);
+        char *th = tab.host(), *td = tab.dev();
         const QwenTables T = qwen_table_layout(d);
         int* src = (int*)(th + T.src);
         int2* hw = (int2*)(th + T.hw);
@@ -309,9 +297,7 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
             max_seg = std::max(max_seg, len);
             mbase += lh * lw;
         }
-        LR_HIP_CHECK(hipMemcpyAsync(td, th, h->tab_bytes, hipMemcpyHostToDevice, st));
-        LR_HIP_CHECK(hipEventRecord(h->tab_ev[slot], st));
-        h->tab_used[slot] = true;
+        tab.commit(st);
         const int* d_src = (const int*)(td + T.src);
         const int2* d_hw = (const int2*)(td + T.hw);
         const int* d_slot2row = (const int*)(td + T.slot2row);
@@ -326,7 +312,7 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         Operand pa = operand16(h->vA, h->vKpad, N, fv);
         linear(h, st, fv, Linear{h->vpatch_w, nullptr, vH, h->vKpad, EPI_OUT_F32, ACT_NONE}, pa, h->vx);
         launch_vit_rope_table(d_hw, N, h->vinv, h->vhd / 4, vhdp / 2, h->vcs, st);
-        const int nvl = h->lim_clip >= 0 && h->lim_clip < d.vit_depth ? h->lim_clip : d.vit_depth;
+        const int nvl = h->n_tower_layers(d.vit_depth);
         const float vscale = 1.0f / std::sqrt((float)h->vhd);
         // (the ViT and merger norms name no reader: they write 16-bit residuals and the GEMM re-encodes them in place)
         for (int l = 0; l < nvl; ++l) {
@@ -363,7 +349,7 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         launch_embed(input_ids, h->img_row, h->wte, h->ev, h->x, Rl, D, d.vocab_size, st);
         launch_mrope_table(h->pos3, Rl, h->inv_s, d.mrope_section[0], d.mrope_section[1], h->half, h->cs, st);
         const int last_pos = (flags & LR_FWD_TRAINING_LAST_TOKEN) ? 1 : 0;
-        h->last_pruned = run_decoder_stack(h, st, attention_mask, B, S, (d.mean_hidden_state || (flags & LR_FWD_KEEP_HIDDEN_STATES)) ? 0 : 1 + last_pos);
+        h->last_pruned = run_decoder_stack(h, st, DecoderPass{attention_mask, B, S, (d.mean_hidden_state || (flags & LR_FWD_KEEP_HIDDEN_STATES)) ? 0 : 1 + last_pos});
         if (d.mean_hidden_state) {      // rw_model:398-406; the as-written SkipCA adds the same vector to every token of a row
             if (d.add_cross_attention) launch_qwen_ca_vec(h->rstat, h->ca_u, B, D, h->tao, st);
             run_mean_pool_head(h, st, attention_mask, B, S, nullptr, 0, h->tao, true, rewards_out);

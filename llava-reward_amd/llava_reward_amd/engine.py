@@ -164,48 +164,57 @@ class RewardEngine:
         self.finalized = True
 
     # ------------------------------------------------------------------ forward
+    @property
+    def _dev(self) -> torch.device:
+        return torch.device("cuda", self.device)
+
+    def _i64(self, t: torch.Tensor) -> torch.Tensor:
+        return t.to(self._dev, torch.int64).contiguous()
+
+    def _pixels(self, pixel_values: torch.Tensor):
+        """(device tensor, its LR_DT_*): bf16 pixels travel as they are, everything else as fp32."""
+        if pixel_values.dtype == torch.bfloat16:
+            return pixel_values.to(self._dev).contiguous(), L.LR_DT_BF16
+        return pixel_values.to(torch.float32).to(self._dev).contiguous(), L.LR_DT_F32
+
+    @staticmethod
+    def _flags(training=False, no_final_norm=False, keep_hidden_states=False) -> int:
+        return ((L.LR_FWD_TRAINING_LAST_TOKEN if training else 0) | (L.LR_FWD_NO_FINAL_NORM if no_final_norm else 0)
+                | (L.LR_FWD_KEEP_HIDDEN_STATES if keep_hidden_states else 0))
+
+    def _rewards(self, B: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+        return out if out is not None else torch.empty(B, self.cfg.value_head_dim, device=self._dev, dtype=torch.float32)
+
+    def _enqueue(self, entry: str, args, inputs) -> None:
+        """lib.<entry>(handle, *args, stream) on the current torch stream; `inputs` stay alive until the stream has consumed them."""
+        stream = torch.cuda.current_stream(self._dev)
+        L.check(self.lib, getattr(self.lib, entry)(self.h, *args, C.c_void_p(stream.cuda_stream)), self.h, entry)
+        for t in inputs:
+            t.record_stream(stream)
+
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: torch.Tensor,
                 image_sizes, training: bool = False, out: Optional[torch.Tensor] = None, no_final_norm: bool = False,
                 keep_hidden_states: bool = False) -> torch.Tensor:
         """keep_hidden_states: run the last decoder layer for every token (LR_FWD_KEEP_HIDDEN_STATES) -- needed before
         last_hidden_state() / read_tap("x"); by default that layer computes only the row each reward is read from."""
-        dev = torch.device("cuda", self.device)
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        mask = attention_mask.to(dev, torch.int64).contiguous()
-        if pixel_values.dtype == torch.bfloat16:
-            pdt = L.LR_DT_BF16
-        else:
-            pixel_values, pdt = pixel_values.to(torch.float32), L.LR_DT_F32
-        pix = pixel_values.to(dev).contiguous()
+        ids, mask = self._i64(input_ids), self._i64(attention_mask)
+        pix, pdt = self._pixels(pixel_values)
         sizes = torch.as_tensor(image_sizes).to("cpu", torch.int64).contiguous()
         B, S = ids.shape
         if pix.dim() != 5 or pix.shape[0] != B:
             raise ValueError("pixel_values must be [B, crops, 3, H, W]")
-        if out is None:
-            out = torch.empty(B, self.cfg.value_head_dim, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lr_forward(self.h, C.c_void_p(ids.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(pix.data_ptr()),
-                                 pdt, C.cast(sizes.data_ptr(), C.POINTER(C.c_int64)), B, S, pix.shape[1],
-                                 (L.LR_FWD_TRAINING_LAST_TOKEN if training else 0) | (L.LR_FWD_NO_FINAL_NORM if no_final_norm else 0)
-                                 | (L.LR_FWD_KEEP_HIDDEN_STATES if keep_hidden_states else 0),
-                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        L.check(self.lib, rc, self.h, "lr_forward")
-        # keep inputs alive until the stream has consumed them
-        for t in (ids, mask, pix):
-            t.record_stream(torch.cuda.current_stream(dev))
+        out = self._rewards(B, out)
+        self._enqueue("lr_forward", (C.c_void_p(ids.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(pix.data_ptr()), pdt,
+                                     C.cast(sizes.data_ptr(), C.POINTER(C.c_int64)), B, S, pix.shape[1],
+                                     self._flags(training, no_final_norm, keep_hidden_states), C.c_void_p(out.data_ptr())), (ids, mask, pix))
         return out
 
     # ------------------------------------------------------------------ shared image prefix (lr_prefix_build / lr_forward_prefixed)
     def prefix_build(self, prefix_ids: torch.Tensor, pixel_values: torch.Tensor, image_size, total_len: int = 0):
         """Cache of the first len(prefix_ids) // 64 * 64 positions of a prompt prefix that holds ONE image (lr_prefix_build).
         Returns (cache: uint8 device tensor, info: _lib.PrefixInfo).  total_len: the width n_shared + T of the batches it will serve."""
-        dev = torch.device("cuda", self.device)
-        ids = prefix_ids.reshape(-1).to(dev, torch.int64).contiguous()
-        if pixel_values.dtype == torch.bfloat16:
-            pdt = L.LR_DT_BF16
-        else:
-            pixel_values, pdt = pixel_values.to(torch.float32), L.LR_DT_F32
-        pix = pixel_values.to(dev).contiguous()
+        ids = self._i64(prefix_ids.reshape(-1))
+        pix, pdt = self._pixels(pixel_values)
         if pix.dim() == 4:
             pix = pix.unsqueeze(0)
         if pix.dim() != 5 or pix.shape[0] != 1:
@@ -216,66 +225,41 @@ class RewardEngine:
         n_prefix = int(ids.numel())
         n_img = int((ids < 0).sum())              # one host read per prefix: sizes the cache
         nbytes = int(self.lib.lr_prefix_bytes(self.h, n_prefix // 64 * 64, n_img))
-        cache = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        cache = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self._dev)
         info = L.PrefixInfo()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lr_prefix_build(self.h, C.c_void_p(ids.data_ptr()), n_prefix, C.c_void_p(pix.data_ptr()), pdt,
-                                      C.cast(size.data_ptr(), C.POINTER(C.c_int64)), pix.shape[1], int(total_len), C.c_void_p(cache.data_ptr()),
-                                      cache.numel(), C.byref(info), C.c_void_p(stream))
-        L.check(self.lib, rc, self.h, "lr_prefix_build")
-        for t in (ids, pix):
-            t.record_stream(torch.cuda.current_stream(dev))
+        self._enqueue("lr_prefix_build", (C.c_void_p(ids.data_ptr()), n_prefix, C.c_void_p(pix.data_ptr()), pdt,
+                                          C.cast(size.data_ptr(), C.POINTER(C.c_int64)), pix.shape[1], int(total_len),
+                                          C.c_void_p(cache.data_ptr()), cache.numel(), C.byref(info)), (ids, pix))
         return cache, info
 
     def forward_prefixed(self, cache: torch.Tensor, info, input_ids: torch.Tensor, attention_mask: torch.Tensor, training: bool = False,
                          out: Optional[torch.Tensor] = None, no_final_norm: bool = False) -> torch.Tensor:
         """Rewards of RIGHT-padded rows [B, T] that hold what follows the cached positions (lr_forward_prefixed)."""
-        dev = torch.device("cuda", self.device)
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        mask = attention_mask.to(dev, torch.int64).contiguous()
+        ids, mask = self._i64(input_ids), self._i64(attention_mask)
         if ids.dim() != 2 or ids.shape != mask.shape:
             raise ValueError("input_ids and attention_mask must be [B, T]")
         B, T = ids.shape
-        if out is None:
-            out = torch.empty(B, self.cfg.value_head_dim, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lr_forward_prefixed(self.h, C.c_void_p(cache.data_ptr()), C.byref(info), C.c_void_p(ids.data_ptr()),
-                                          C.c_void_p(mask.data_ptr()), B, T,
-                                          (L.LR_FWD_TRAINING_LAST_TOKEN if training else 0) | (L.LR_FWD_NO_FINAL_NORM if no_final_norm else 0),
-                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        L.check(self.lib, rc, self.h, "lr_forward_prefixed")
-        for t in (ids, mask, cache):
-            t.record_stream(torch.cuda.current_stream(dev))
+        out = self._rewards(B, out)
+        self._enqueue("lr_forward_prefixed", (C.c_void_p(cache.data_ptr()), C.byref(info), C.c_void_p(ids.data_ptr()), C.c_void_p(mask.data_ptr()),
+                                              B, T, self._flags(training, no_final_norm), C.c_void_p(out.data_ptr())), (ids, mask, cache))
         return out
 
     def forward_qwen(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: torch.Tensor,
                      image_grid_thw, training: bool = False, out: Optional[torch.Tensor] = None,
                      keep_hidden_states: bool = False) -> torch.Tensor:
         """The qwen branch's inputs_batch (rw_model_general_preference.py:354-357): pixel_values [sum t*h*w, 1176]."""
-        dev = torch.device("cuda", self.device)
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        mask = attention_mask.to(dev, torch.int64).contiguous()
-        if pixel_values.dtype == torch.bfloat16:
-            pdt = L.LR_DT_BF16
-        else:
-            pixel_values, pdt = pixel_values.to(torch.float32), L.LR_DT_F32
-        pix = pixel_values.to(dev).contiguous()
+        ids, mask = self._i64(input_ids), self._i64(attention_mask)
+        pix, pdt = self._pixels(pixel_values)
         grid = torch.as_tensor(image_grid_thw).to("cpu", torch.int64).contiguous()
         B, S = ids.shape
         if grid.dim() != 2 or grid.shape[1] != 3:
             raise ValueError("image_grid_thw must be [n_images, 3]")
         if pix.dim() != 2 or pix.shape[1] != self.cfg.vision.patch_dim or pix.shape[0] != int(grid.prod(dim=1).sum()):
             raise ValueError("pixel_values must be [sum(t*h*w), in_ch*temporal_patch*patch^2] matching image_grid_thw")
-        if out is None:
-            out = torch.empty(B, self.cfg.value_head_dim, device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self.lib.lr_forward_qwen(self.h, C.c_void_p(ids.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(pix.data_ptr()),
-                                      pdt, C.cast(grid.data_ptr(), C.POINTER(C.c_int64)), grid.shape[0], B, S,
-                                      (L.LR_FWD_TRAINING_LAST_TOKEN if training else 0) | (L.LR_FWD_KEEP_HIDDEN_STATES if keep_hidden_states else 0),
-                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        L.check(self.lib, rc, self.h, "lr_forward_qwen")
-        for t in (ids, mask, pix):
-            t.record_stream(torch.cuda.current_stream(dev))
+        out = self._rewards(B, out)
+        self._enqueue("lr_forward_qwen", (C.c_void_p(ids.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(pix.data_ptr()), pdt,
+                                          C.cast(grid.data_ptr(), C.POINTER(C.c_int64)), grid.shape[0], B, S,
+                                          self._flags(training, keep_hidden_states=keep_hidden_states), C.c_void_p(out.data_ptr())), (ids, mask, pix))
         return out
 
     def last_hidden_state(self, B: int, S: int, no_final_norm: bool = False) -> torch.Tensor:

@@ -122,6 +122,42 @@ def test_long_factor_set():
     assert torch.isfinite(got).all() and torch.equal(got, want)
 
 
+# (dtype, precision map, site overrides) that put two operand forms into ONE cache.  layers: layer 0 keeps the descriptor's split
+# operands, layer 1 runs a single pass -- two row widths, the cache's per-layer stride follows the attention site.  sites: every layer in
+# the default form with its attention site strict while the qkv site that writes the cached rows stays default.
+MIXED = {
+    "layers": ("f16x2", (-1, 0, 1, 0), ()),
+    "sites": ("f16x2f8", (-1, 2, 0, 0), (2, 1, 2, 2, 2)),
+}
+
+
+@pytest.mark.parametrize("mix", ["layers", "sites"])
+def test_mixed_operand_forms_in_one_cache(mix):
+    dtype, pmap, sites = MIXED[mix]
+    c = CASES["a"]
+    cfg = _cfg()
+    batch = _one_image_batch(cfg, c["lens"], c["grid"], c["common"])
+    m = _model(cfg, dtype, calibrate=False)
+    eng = m.engine
+    plain = _both(m, batch)[3]                                       # a state built under the map the model came with
+    eng.set_precision_map(*pmap)                                     # the mixed map, BEFORE build_prefix
+    eng.set_precision_sites(*sites)
+    want, got, plan, state = _both(m, batch)
+    assert plan == c["plan"]
+    assert torch.isfinite(got).all()
+    assert torch.equal(got, want), (got - want).abs().max().item()
+    if mix == "layers":
+        assert state.nbytes < plain.nbytes                           # (layer 1's rows are half as wide)
+    rp = synth.right_pad(batch)
+    ids, mask = (torch.from_numpy(rp[k][:, plan[1]:]).cuda() for k in ("input_ids", "attention_mask"))
+    with pytest.raises(Exception, match="stale prefix cache"):       # each state is refused under the other map
+        m.forward_prefixed(plain, ids, mask)
+    eng.set_precision_sites()
+    eng.set_precision_map(-1, -1, 0, 0)
+    with pytest.raises(Exception, match="stale prefix cache"):
+        m.forward_prefixed(state, ids, mask)
+
+
 # ---- score_captions: prompts built as inference_process_phi3v builds them, from an image ----
 def _rows_of(tok, image, captions, num_crops=1):
     pix, sizes, ntok = hd_transform_batch([_load_rgb(image)], num_crops, "cuda")
