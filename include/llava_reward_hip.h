@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LR_ABI_VERSION 10
+#define LR_ABI_VERSION 11
 
 enum { LR_OK = 0, LR_EINVAL = 1, LR_EHIP = 2, LR_ESTATE = 3, LR_ENOTFOUND = 4, LR_ENOMEM = 5 };
 enum { LR_DT_BF16 = 0, LR_DT_F16 = 1, LR_DT_F32 = 2 };
@@ -325,6 +325,33 @@ int lr_op_gemm_bt_mixed(void* A, const void* W, void* W8, void* scratch, void* C
                         int operand_dtype, int flags, int* wexp, void* hip_stream);
 int lr_op_norm_rows(const float* x, const float* w, const float* b, void* y, int rows, int H, float eps,
                     int operand_dtype, void* hip_stream);
+/* The row kernels between the GEMMs, one launch each (ABI 11; arguments as the launchers of csrc/kernels.h, all pointers DEVICE).
+ * lr_op_norm_rows_ex: prec = 1 stores rows [hi | lo] (2H wide); group g: g consecutive input rows form one output row (H % 8 != 0 or
+ * g > 1 run the 4-wide kernel); lo8_scales != NULL: the residual half as e4m3 bytes + E8M0 block scales (csrc/common.h lo8_scale_at,
+ * lr_op_lo8_scratch_bytes(rows, H) bytes; prec = 1, group = 1, H % 128 == 0).  H % 4 == 0, H <= 4096, rows % group == 0. */
+int lr_op_norm_rows_ex(const float* x, const float* w, const float* b, void* y, int rows, int H, float eps, int operand_dtype, int prec,
+                       int group, unsigned char* lo8_scales, void* hip_stream);
+/* C [M, N] (ldc) = alpha * A [M, K] (lda) * op(B), fp32 on v_mfma_f32_32x32x2_f32 (ABI 11): b_nt = 1: B [N, K] (C = A B^T), 0: B [K, N];
+ * b_is_bf16: B holds bf16 bits.  Any M, N, K >= 0. */
+int lr_op_gemm_f32(const float* A, const void* B, int b_is_bf16, int b_nt, float* C, int M, int N, int K, int lda, int ldb, int ldc,
+                   float alpha, void* hip_stream);
+/* The fp32 reward tail, kernel by kernel (ABI 11).  tstat: int32 [B][4] = {last valid, first valid, image slots, valid tokens};
+ * voff: int32 image-row offsets; voff_stride 1: row b reads ev rows voff[b] .. voff[b + 1], 0: every row reads voff[0] .. voff[1].
+ * rowvec_linear K % 4 == 0, ca_scores D % 4 == 0, ca_pool D <= 4096 (LR_EINVAL otherwise). */
+int lr_op_gather_norm_rows(const float* x, const int* tstat, int S, int use_last_pos, const float* w, float eps, float* y, int B, int D,
+                           void* hip_stream);
+int lr_op_rowvec_linear(const float* x, const float* W, float* y, int B, int N, int K, void* hip_stream);
+int lr_op_ca_scores(const float* ev, const float* kq, const int* voff, int B, int Vmax, int D, float scale, float* sc, int voff_stride,
+                    void* hip_stream);
+int lr_op_ca_softmax(float* sc, int B, int Vmax, void* hip_stream);
+int lr_op_ca_context(const float* ev, const float* pr, const int* voff, int B, int Vmax, int D, float* ctx, int voff_stride,
+                     void* hip_stream);
+int lr_op_reward_head(const float* hL, const float* attn_o, const float* ca_w, float ca_eps, const float* vh, int d, float* out, int B,
+                      int D, void* hip_stream);
+int lr_op_rms_rows_f32(const float* x, const float* w, float eps, float* y, int rows, int D, void* hip_stream);
+int lr_op_ca_softmax_pad(float* sc, int rows, int ld, int vb, int Vmax, void* hip_stream);
+int lr_op_ca_pool(const float* h, const float* o, const float* u, const float* ca_w, float ca_eps, const int64_t* mask, float* pooled,
+                  int B, int S, int D, void* hip_stream);
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std, float offset, int bf16_round,
                      void* hip_stream);
 

@@ -1133,6 +1133,57 @@ int lr_op_norm_rows(const float* x, const float* w, const float* b, void* y, int
     return op_guard([&] { launch_norm_rows(x, w, b, y, rows, H, eps, op_dtype(operand_dtype), (hipStream_t)hip_stream); });
 }
 
+int lr_op_norm_rows_ex(const float* x, const float* w, const float* b, void* y, int rows, int H, float eps, int operand_dtype, int prec,
+                       int group, unsigned char* lo8_scales, void* hip_stream) {
+    return op_guard([&] { launch_norm_rows(x, w, b, y, rows, H, eps, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec, group, lo8_scales); });
+}
+
+int lr_op_gemm_f32(const float* A, const void* B, int b_is_bf16, int b_nt, float* C, int M, int N, int K, int lda, int ldb, int ldc,
+                   float alpha, void* hip_stream) {
+    return op_guard([&] { launch_gemm_f32(A, B, b_is_bf16, b_nt, C, M, N, K, lda, ldb, ldc, alpha, (hipStream_t)hip_stream); });
+}
+
+int lr_op_gather_norm_rows(const float* x, const int* tstat, int S, int use_last_pos, const float* w, float eps, float* y, int B, int D,
+                           void* hip_stream) {
+    return op_guard([&] { launch_gather_norm_rows(x, tstat, S, use_last_pos, w, eps, y, B, D, (hipStream_t)hip_stream); });
+}
+
+int lr_op_rowvec_linear(const float* x, const float* W, float* y, int B, int N, int K, void* hip_stream) {
+    return op_guard([&] { launch_rowvec_linear(x, W, y, B, N, K, (hipStream_t)hip_stream); });
+}
+
+int lr_op_ca_scores(const float* ev, const float* kq, const int* voff, int B, int Vmax, int D, float scale, float* sc, int voff_stride,
+                    void* hip_stream) {
+    return op_guard([&] { launch_ca_scores(ev, kq, voff, B, Vmax, D, scale, sc, (hipStream_t)hip_stream, voff_stride); });
+}
+
+int lr_op_ca_softmax(float* sc, int B, int Vmax, void* hip_stream) {
+    return op_guard([&] { launch_ca_softmax(sc, B, Vmax, (hipStream_t)hip_stream); });
+}
+
+int lr_op_ca_context(const float* ev, const float* pr, const int* voff, int B, int Vmax, int D, float* ctx, int voff_stride,
+                     void* hip_stream) {
+    return op_guard([&] { launch_ca_context(ev, pr, voff, B, Vmax, D, ctx, (hipStream_t)hip_stream, voff_stride); });
+}
+
+int lr_op_reward_head(const float* hL, const float* attn_o, const float* ca_w, float ca_eps, const float* vh, int d, float* out, int B,
+                      int D, void* hip_stream) {
+    return op_guard([&] { launch_reward_head(hL, attn_o, ca_w, ca_eps, vh, d, out, B, D, (hipStream_t)hip_stream); });
+}
+
+int lr_op_rms_rows_f32(const float* x, const float* w, float eps, float* y, int rows, int D, void* hip_stream) {
+    return op_guard([&] { launch_rms_rows_f32(x, w, eps, y, rows, D, (hipStream_t)hip_stream); });
+}
+
+int lr_op_ca_softmax_pad(float* sc, int rows, int ld, int vb, int Vmax, void* hip_stream) {
+    return op_guard([&] { launch_ca_softmax_pad(sc, rows, ld, vb, Vmax, (hipStream_t)hip_stream); });
+}
+
+int lr_op_ca_pool(const float* h, const float* o, const float* u, const float* ca_w, float ca_eps, const int64_t* mask, float* pooled,
+                  int B, int S, int D, void* hip_stream) {
+    return op_guard([&] { launch_ca_pool(h, o, u, ca_w, ca_eps, mask, pooled, B, S, D, (hipStream_t)hip_stream); });
+}
+
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std_, float offset, int bf16_round,
                      void* hip_stream) {
     return op_guard([&] { launch_synth_fill(out, n, tensor_seed(seed, name), uniform_scale(std_), offset, bf16_round, (hipStream_t)hip_stream); });

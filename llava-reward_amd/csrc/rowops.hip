@@ -675,6 +675,7 @@ __global__ __launch_bounds__(256) void ca_scores_kernel(const float* __restrict_
 void launch_ca_scores(const float* ev, const float* kq, const int* voff, int B, int Vmax, int D, float scale, float* sc,
                       hipStream_t st, int voff_stride) {
     if (B <= 0 || Vmax <= 0) return;
+    if (D % 4) throw std::runtime_error("ca_scores: D must be a multiple of 4");
     hipLaunchKernelGGL(ca_scores_kernel, dim3(cdiv(Vmax, 4), B), dim3(256), 0, st, ev, kq, voff, Vmax, D, scale, sc, voff_stride);
 }
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from helpers import gemm_ref as gr
+from helpers.rowops_ref import lo8_scales_decode
 from llava_reward_amd import _lib as L
 
 pytestmark = pytest.mark.gpu
@@ -156,11 +157,8 @@ def run(lib, kform, dt, M, N, K, *, family="normal", epi=gr.EPI_OUT_F32, act=0, 
             assert bool((raw[:, nout:] == S8).all()), "write behind the one-byte residual half"
             lo8v = raw[:, :nout].contiguous().view(torch.float8_e4m3fn).double()
             s2 = bufs["scratch"][lib.lr_op_lo8_scratch_bytes(M, K):]
-            Mb, nkb = (M + 255) // 256, nout // 128
-            planes = s2[: Mb * 1024 * ((nkb + 3) // 4)].view((nkb + 3) // 4, Mb, 4, 256).permute(0, 2, 1, 3).reshape(-1, Mb, 256)[:nkb]
-            r = torch.arange(256, device=DEV)
-            sidx = ((((r >> 6) & 1) * 16 + (r & 15)) * 2 + (r >> 7)) * 4 + ((r >> 4) & 3)
-            E = planes[:, :, sidx].reshape(nkb, Mb * 256)[:, :M].t().double()
+            nkb = nout // 128
+            E = lo8_scales_decode(s2, M, nout).double()
             lo_val = (lo8v.view(M, nkb, 128) * torch.exp2(E - 127)[:, :, None]).view(M, nout)
         Pg = Pb.to(DEV)
         worst, maxerr, bits_ok = 0.0, 0.0, True

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers.rowops_ref import lo8_scales_decode
 from llava_reward_amd import _lib as L
 from llava_reward_amd import synth
 
@@ -578,11 +579,7 @@ def test_gemm_e4m3_residual_pass_matches_fp64(lib):
         # 4 K-tiles and 256-row tile in the consuming kernel's lane order (csrc/common.h lo8_scale_at): decode, compare with the f16
         # residuals -- every element within 2^-4 of its BLOCK's maximum
         lo8 = A_work[:, K:].contiguous().view(torch.uint8)[:, :K].contiguous().view(torch.float8_e4m3fn).float()
-        Mb, nkb = (M + 255) // 256, K // 128
-        planes = aexp[: Mb * 1024 * ((nkb + 3) // 4)].view((nkb + 3) // 4, Mb, 4, 256).permute(0, 2, 1, 3).reshape(-1, Mb, 256)[:nkb]   # [kblock, Mb, 256]
-        r = torch.arange(256, device="cuda")
-        sidx = ((((r >> 6) & 1) * 16 + (r & 15)) * 2 + (r >> 7)) * 4 + ((r >> 4) & 3)
-        E = planes[:, :, sidx].reshape(nkb, Mb * 256)[:, :M].t().float()                  # [M, K / 128]
+        E = lo8_scales_decode(aexp, M, K).float()                  # [M, K / 128]
         dec = (lo8.view(M, K // 128, 128) * torch.exp2(E - 127)[:, :, None]).view(M, K)
         ref_lo = lo.float()
         bmax = ref_lo.view(M, K // 128, 128).abs().amax(dim=2, keepdim=True).expand(M, K // 128, 128).reshape(M, K)
@@ -665,11 +662,8 @@ def test_gemm_e4m3_residuals_written_by_the_producing_epilogue(lib):
         # decode h's residual half
         hh = h_bytes[:, :Kh].float()
         lo8 = h_bytes[:, Kh:].contiguous().view(torch.uint8)[:, :Kh].contiguous().view(torch.float8_e4m3fn).float()
-        Mb, nkb = (M + 255) // 256, Kh // 128
-        planes = h_scales[: Mb * 1024 * ((nkb + 3) // 4)].view((nkb + 3) // 4, Mb, 4, 256).permute(0, 2, 1, 3).reshape(-1, Mb, 256)[:nkb]
-        r = torch.arange(256, device="cuda")
-        sidx = ((((r >> 6) & 1) * 16 + (r & 15)) * 2 + (r >> 7)) * 4 + ((r >> 4) & 3)
-        E = planes[:, :, sidx].reshape(nkb, Mb * 256)[:, :M].t().float()
+        nkb = Kh // 128
+        E = lo8_scales_decode(h_scales, M, Kh).float()
         dec = (lo8.view(M, nkb, 128) * torch.exp2(E - 127)[:, :, None]).view(M, Kh)
         # the epilogue's own fp32 h is not visible; hi + decoded lo must sit closer to the fp64 h than hi alone by ~2^-4 of the f16 step
         e_hi = (hh.double() - h_ref).abs()
