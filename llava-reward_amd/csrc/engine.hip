@@ -19,9 +19,9 @@ void build_weight_table_phi(lr_engine* e) {
     vec_slot(e, ep + "sub_GN", {1, 1, 1, 4 * Hc}, e->sub_gn, 0.02, 0);
     e->p0_w = oalloc(e, (size_t)D * 4 * Hc); e->p0_b = falloc(e, D);
     e->p2_w = oalloc(e, (size_t)D * D); e->p2_b = falloc(e, D);
-    add_slot(e, ep + "img_projection.0.weight", {D, 4 * Hc}, e->p0_w, 4 * Hc, 4 * Hc, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, ep + "img_projection.0.weight", {D, 4 * Hc}, e->p0_w->hi, 4 * Hc, 4 * Hc, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, ep + "img_projection.0.bias", {D}, e->p0_b, 0.02, 0);
-    add_slot(e, ep + "img_projection.2.weight", {D, D}, e->p2_w, D, D, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, ep + "img_projection.2.weight", {D, D}, e->p2_w->hi, D, D, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, ep + "img_projection.2.bias", {D}, e->p2_b, 0.02, 0);
     e->dl.resize(d.layers);
     for (int l = 0; l < d.layers; ++l) {
@@ -31,12 +31,12 @@ void build_weight_table_phi(lr_engine* e) {
         L.qkv_w = oalloc(e, (size_t)3 * D * D); L.o_w = oalloc(e, (size_t)D * D);
         L.gu_w = oalloc(e, (size_t)2 * I * D); L.down_w = oalloc(e, (size_t)D * I);
         vec_slot(e, p + "input_layernorm.weight", {D}, L.ln1, 0.05, 1.0);
-        add_slot(e, p + "self_attn.qkv_proj.weight", {3 * D, D}, L.qkv_w, D, D, od, PACK_ROPE_QKV, 0.02, 0);
+        add_slot(e, p + "self_attn.qkv_proj.weight", {3 * D, D}, L.qkv_w->hi, D, D, od, PACK_ROPE_QKV, 0.02, 0);
         e->slots.back().aux_d = D; e->slots.back().aux_hd = e->hd;
-        add_slot(e, p + "self_attn.o_proj.weight", {D, D}, L.o_w, D, D, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "self_attn.o_proj.weight", {D, D}, L.o_w->hi, D, D, od, PACK_PLAIN, 0.02, 0);
         vec_slot(e, p + "post_attention_layernorm.weight", {D}, L.ln2, 0.05, 1.0);
-        add_slot(e, p + "mlp.gate_up_proj.weight", {2 * I, D}, L.gu_w, D, D, od, PACK_SWIGLU, 0.02, 0);
-        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w, I, I, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "mlp.gate_up_proj.weight", {2 * I, D}, L.gu_w->hi, D, D, od, PACK_SWIGLU, 0.02, 0);
+        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w->hi, I, I, od, PACK_PLAIN, 0.02, 0);
         if (d.lora_rank > 0) {      // utils/utils.py:194-222 create_lora_config: qkv_proj, o_proj, gate_up_proj, down_proj
             register_lora(e, L.lqkv, p + "self_attn.qkv_proj", 3 * D, D, 0, 1, 3 * D, 0, PACK_ROPE_QKV, D, e->hd);
             register_lora(e, L.lo, p + "self_attn.o_proj", D, D, 0, 1, D, 0, PACK_PLAIN);
@@ -71,9 +71,9 @@ void build_weight_table_llava(lr_engine* e) {
     register_clip(e, "vision_tower.vision_model.");
     e->p0_w = oalloc(e, (size_t)D * Hc); e->p0_b = falloc(e, D);
     e->p2_w = oalloc(e, (size_t)D * D); e->p2_b = falloc(e, D);
-    add_slot(e, "multi_modal_projector.linear_1.weight", {D, Hc}, e->p0_w, Hc, Hc, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, "multi_modal_projector.linear_1.weight", {D, Hc}, e->p0_w->hi, Hc, Hc, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, "multi_modal_projector.linear_1.bias", {D}, e->p0_b, 0.02, 0);
-    add_slot(e, "multi_modal_projector.linear_2.weight", {D, D}, e->p2_w, D, D, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, "multi_modal_projector.linear_2.weight", {D, D}, e->p2_w->hi, D, D, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, "multi_modal_projector.linear_2.bias", {D}, e->p2_b, 0.02, 0);
     e->newline = falloc(e, D);
     vec_slot(e, "image_newline", {D}, e->newline, 0.02, 0);
@@ -86,16 +86,16 @@ void build_weight_table_llava(lr_engine* e) {
         L.gu_w = oalloc(e, (size_t)2 * I * D); L.down_w = oalloc(e, (size_t)D * I);
         vec_slot(e, p + "input_layernorm.weight", {D}, L.ln1, 0.05, 1.0);
         // q, k, v land in one fused [Hq + 2 Hkv, D] matrix; q and k rows pair-interleaved per head for the RoPE epilogue
-        add_slot(e, p + "self_attn.q_proj.weight", {Hq, D}, L.qkv_w, D, D, od, PACK_ROPE_QKV, 0.02, 0);
+        add_slot(e, p + "self_attn.q_proj.weight", {Hq, D}, L.qkv_w->hi, D, D, od, PACK_ROPE_QKV, 0.02, 0);
         e->slots.back().aux_d = Hq; e->slots.back().aux_hd = hd;
-        add_slot(e, p + "self_attn.k_proj.weight", {Hkv, D}, (char*)L.qkv_w + (size_t)Hq * D * 2, D, D, od, PACK_ROPE_QKV, 0.02, 0);
+        add_slot(e, p + "self_attn.k_proj.weight", {Hkv, D}, L.qkv_w->hi + (size_t)Hq * D * 2, D, D, od, PACK_ROPE_QKV, 0.02, 0);
         e->slots.back().aux_d = Hkv; e->slots.back().aux_hd = hd;
-        add_slot(e, p + "self_attn.v_proj.weight", {Hkv, D}, (char*)L.qkv_w + (size_t)(Hq + Hkv) * D * 2, D, D, od, PACK_PLAIN, 0.02, 0);
-        add_slot(e, p + "self_attn.o_proj.weight", {D, Hq}, L.o_w, Hq, Hq, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "self_attn.v_proj.weight", {Hkv, D}, L.qkv_w->hi + (size_t)(Hq + Hkv) * D * 2, D, D, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "self_attn.o_proj.weight", {D, Hq}, L.o_w->hi, Hq, Hq, od, PACK_PLAIN, 0.02, 0);
         vec_slot(e, p + "post_attention_layernorm.weight", {D}, L.ln2, 0.05, 1.0);
-        add_slot(e, p + "mlp.gate_proj.weight", {I, D}, L.gu_w, D, D, od, PACK_SWIGLU_GATE, 0.02, 0);
-        add_slot(e, p + "mlp.up_proj.weight", {I, D}, L.gu_w, D, D, od, PACK_SWIGLU_UP, 0.02, 0);
-        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w, I, I, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "mlp.gate_proj.weight", {I, D}, L.gu_w->hi, D, D, od, PACK_SWIGLU_GATE, 0.02, 0);
+        add_slot(e, p + "mlp.up_proj.weight", {I, D}, L.gu_w->hi, D, D, od, PACK_SWIGLU_UP, 0.02, 0);
+        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w->hi, I, I, od, PACK_PLAIN, 0.02, 0);
         if (d.lora_rank > 0) {      // utils/utils.py:243-262 create_lora_config_llava16_vicuna: q, k, v, o, gate, up, down of every layer
             register_lora(e, L.lqkv, p + "self_attn.q_proj", e->Nqkv, D, 0, 3, Hq, 0, PACK_ROPE_QKV, Hq, hd);
             register_lora(e, L.lqkv, p + "self_attn.k_proj", e->Nqkv, D, 1, 3, Hkv, Hq, PACK_ROPE_QKV, Hkv, hd);
@@ -128,11 +128,11 @@ void ensure_stage(lr_engine* e, size_t raw_bytes, size_t n_f32) {
 
 void pack_slot(lr_engine* e, Slot& s, const float* src_f32) {
     if (s.lo_dst && !e->inexact_dev) {
-        LR_HIP_CHECK(hipMalloc((void**)&e->inexact_dev, e->wbufs.size() * sizeof(int)));
-        LR_HIP_CHECK(hipMemset(e->inexact_dev, 0, e->wbufs.size() * sizeof(int)));
+        LR_HIP_CHECK(hipMalloc((void**)&e->inexact_dev, e->weights.size() * sizeof(int)));
+        LR_HIP_CHECK(hipMemset(e->inexact_dev, 0, e->weights.size() * sizeof(int)));
     }
     launch_pack(src_f32, s.dst, s.rows, s.cols, s.ld_dst, s.mode == PACK_TRANSPOSE ? s.cols : s.cols_dst, s.dst_dtype, s.mode, 0,
-                s.aux_d, s.aux_hd, s.aux_hdp, s.lo_dst, s.lo_dst ? e->inexact_dev + s.wid : nullptr);
+                s.aux_d, s.aux_hd, s.aux_hdp, s.lo_dst, s.lo_dst ? e->inexact_dev + s.weight->id : nullptr);
     s.provided = true;
 }
 
@@ -586,29 +586,11 @@ int lr_upload_weight(lr_handle h, const char* name, const void* data, const int6
             launch_cvt_to_f32(dev_src, op_dtype(dtype), h->stage_f32, n, 0);
             f32 = h->stage_f32;
         }
-        if (s.wid >= 0 && s.lo_dst) {          // split-operand mode: this tensor's buffer has a residual twin
-            const lr_engine::WBuf& wb = h->wbufs[s.wid];
-            if (h->own8.count(wb.hi)) {        // adapter matrix: its e4m3 twin is a separate buffer, rebuilt at the next launch
-                h->w8exp.erase(wb.hi); h->w8exp2.erase(wb.hi);
-            } else if (h->w8exp.count(wb.hi)) {       // its e4m3 twin has been prepared (default parity mode, after lr_finalize)
-                const bool whole = (size_t)s.rows * s.ld_dst * 2 == wb.bytes && s.dst == wb.hi;
-                const bool was_inexact = !h->inexact.empty() && h->inexact[s.wid];
-                // an exact buffer's residual twin holds e4m3(W) now (its 16-bit residuals were all zero); an inexact buffer's still
-                // holds the 16-bit residuals (its e4m3 rows live in pair8)
-                if (!whole && !was_inexact) LR_HIP_CHECK(hipMemset(wb.lo, 0, wb.bytes));
-                h->w8exp.erase(wb.hi); h->w8exp2.erase(wb.hi);
-            }
-        }
-        if (s.wid >= 0 && s.lo_dst && h->inexact_dev && (size_t)s.rows * s.ld_dst * 2 == h->wbufs[s.wid].bytes && s.dst == h->wbufs[s.wid].hi)
-            LR_HIP_CHECK(hipMemset(h->inexact_dev + s.wid, 0, sizeof(int)));      // the whole buffer is replaced: it may be exact again
+        if (s.weight) h->weight_changed(*s.weight, s.dst, (size_t)s.rows * s.ld_dst * 2);
         pack_slot(h, s, f32);
         ++h->weights_epoch;
-        h->w8.clear();             // W8A8 twins are separate buffers, rebuilt from the packed weights at the next launch
         LR_HIP_CHECK(hipStreamSynchronize(0));
-        if (h->finalized && h->inexact_dev) {    // a re-upload after lr_finalize may have made a buffer inexact -- or exact again
-            LR_HIP_CHECK(hipMemcpy(h->inexact.data(), h->inexact_dev, h->wbufs.size() * sizeof(int), hipMemcpyDeviceToHost));
-            h->release_stale_pair8();
-        }
+        if (h->finalized) h->read_back_inexact();      // a re-upload after lr_finalize may have made a buffer inexact -- or exact again
     });
 }
 
@@ -617,7 +599,7 @@ int lr_synth_weights(lr_handle h, uint64_t seed) { return lr_synth_weights_ex(h,
 int lr_synth_weights_ex(lr_handle h, uint64_t seed, int flags) {
     if (!h) return LR_EINVAL;
     return guarded(h, [&] {
-        if (h->inexact_dev) LR_HIP_CHECK(hipMemset(h->inexact_dev, 0, h->wbufs.size() * sizeof(int)));   // every buffer is rewritten below
+        for (Weight& w : h->weights) h->weight_changed(w, w.hi, w.bytes);      // every buffer is rewritten below
         for (Slot& s : h->slots) {
             const size_t n = (size_t)s.rows * s.cols;
             ensure_stage(h, 0, n);
@@ -629,14 +611,9 @@ int lr_synth_weights_ex(lr_handle h, uint64_t seed, int flags) {
                 launch_synth_fill(h->stage_f32, n, ts, uniform_scale(s.std_), (float)s.offset, (flags & 1) ? 0 : 1, 0);
             pack_slot(h, s, h->stage_f32);
         }
-        h->w8exp.clear(); h->w8exp2.clear(); h->w8.clear();
         ++h->weights_epoch;
         LR_HIP_CHECK(hipStreamSynchronize(0));
-        if (h->finalized && h->inexact_dev) {    // re-synthesised after lr_finalize (fp32-valued profile): a buffer may have become inexact
-            h->inexact.resize(h->wbufs.size(), 0);
-            LR_HIP_CHECK(hipMemcpy(h->inexact.data(), h->inexact_dev, h->wbufs.size() * sizeof(int), hipMemcpyDeviceToHost));
-            h->release_stale_pair8();
-        }
+        if (h->finalized) h->read_back_inexact();      // re-synthesised after lr_finalize (fp32-valued profile): a buffer may have become inexact
     });
 }
 
@@ -648,10 +625,7 @@ int lr_finalize(lr_handle h) {
         if (h->finalized) return;
         for (const Slot& s : h->slots)
             if (!s.provided) throw std::logic_error("lr_finalize: tensor never provided: " + s.name);
-        if (h->inexact_dev) {           // which operand-weight buffers carry non-zero rounding residuals (split-operand mode)
-            h->inexact.assign(h->wbufs.size(), 0);
-            LR_HIP_CHECK(hipMemcpy(h->inexact.data(), h->inexact_dev, h->wbufs.size() * sizeof(int), hipMemcpyDeviceToHost));
-        }
+        h->read_back_inexact();         // which operand-weight buffers carry non-zero rounding residuals (split-operand mode)
         if (h->stage_raw) { LR_HIP_CHECK(hipFree(h->stage_raw)); h->stage_raw = nullptr; h->stage_raw_cap = 0; }
         if (h->stage_f32) { LR_HIP_CHECK(hipFree(h->stage_f32)); h->stage_f32 = nullptr; h->stage_f32_cap = 0; }
         if (h->qwen) { finalize_qwen(h); h->finalized = true; return; }

@@ -77,7 +77,7 @@ void build_weight_table_qwen(lr_engine* e) {
     e->wte = (unsigned short*)e->dalloc((size_t)d.vocab_size * D * 2, true);      // bf16 embedding table (not an MFMA operand)
     add_slot(e, "model.embed_tokens.weight", {d.vocab_size, D}, e->wte, D, D, DT_BF16, PACK_PLAIN, 0.02, 0);
     e->vpatch_w = oalloc(e, (size_t)vH * e->vKpad);
-    add_slot(e, "visual.patch_embed.proj.weight", {vH, d.vit_in_ch, d.vit_temporal_patch, d.vit_patch, d.vit_patch}, e->vpatch_w,
+    add_slot(e, "visual.patch_embed.proj.weight", {vH, d.vit_in_ch, d.vit_temporal_patch, d.vit_patch, d.vit_patch}, e->vpatch_w->hi,
              e->vKpad, e->vKpad, od, PACK_PLAIN, 0.02, 0);
     e->vl.resize(d.vit_depth);
     for (int l = 0; l < d.vit_depth; ++l) {
@@ -90,31 +90,31 @@ void build_weight_table_qwen(lr_engine* e) {
         L.down_w = oalloc(e, (size_t)vH * vIp); L.down_b = falloc(e, vH);
         vec_slot(e, p + "norm1.weight", {vH}, L.n1, 0.05, 1.0);
         // fused qkv [3 * vH, vH]: heads widened to vhdp, q and k dims pair-interleaved for the RoPE epilogue; bias alike
-        add_slot(e, p + "attn.qkv.weight", {3 * vH, vH}, L.qkv_w, vH, vH, od, PACK_ROPE_QKV, 0.02, 0);
+        add_slot(e, p + "attn.qkv.weight", {3 * vH, vH}, L.qkv_w->hi, vH, vH, od, PACK_ROPE_QKV, 0.02, 0);
         e->slots.back().aux_d = vH; e->slots.back().aux_hd = vhd; e->slots.back().aux_hdp = vhdp;
         add_slot(e, p + "attn.qkv.bias", {3 * vH}, L.qkv_b, 1, 1, DT_F32, PACK_ROPE_QKV, 0.02, 0);
         e->slots.back().rows = 3 * vH; e->slots.back().cols = 1;
         e->slots.back().aux_d = vH; e->slots.back().aux_hd = vhd; e->slots.back().aux_hdp = vhdp;
-        add_slot(e, p + "attn.proj.weight", {vH, vH}, L.proj_w, vHp, vH, od, PACK_HEADPAD_COLS, 0.02, 0);
+        add_slot(e, p + "attn.proj.weight", {vH, vH}, L.proj_w->hi, vHp, vH, od, PACK_HEADPAD_COLS, 0.02, 0);
         e->slots.back().aux_hd = vhd; e->slots.back().aux_hdp = vhdp;
         vec_slot(e, p + "attn.proj.bias", {vH}, L.proj_b, 0.02, 0);
         vec_slot(e, p + "norm2.weight", {vH}, L.n2, 0.05, 1.0);
-        add_slot(e, p + "mlp.gate_proj.weight", {vI, vH}, L.gu_w, vH, vH, od, PACK_SWIGLU_GATE, 0.02, 0);
+        add_slot(e, p + "mlp.gate_proj.weight", {vI, vH}, L.gu_w->hi, vH, vH, od, PACK_SWIGLU_GATE, 0.02, 0);
         add_slot(e, p + "mlp.gate_proj.bias", {vI}, L.gu_b, 1, 1, DT_F32, PACK_SWIGLU_GATE, 0.02, 0);
         e->slots.back().rows = vI; e->slots.back().cols = 1;
-        add_slot(e, p + "mlp.up_proj.weight", {vI, vH}, L.gu_w, vH, vH, od, PACK_SWIGLU_UP, 0.02, 0);
+        add_slot(e, p + "mlp.up_proj.weight", {vI, vH}, L.gu_w->hi, vH, vH, od, PACK_SWIGLU_UP, 0.02, 0);
         add_slot(e, p + "mlp.up_proj.bias", {vI}, L.gu_b, 1, 1, DT_F32, PACK_SWIGLU_UP, 0.02, 0);
         e->slots.back().rows = vI; e->slots.back().cols = 1;
-        add_slot(e, p + "mlp.down_proj.weight", {vH, vI}, L.down_w, vIp, vIp, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "mlp.down_proj.weight", {vH, vI}, L.down_w->hi, vIp, vIp, od, PACK_PLAIN, 0.02, 0);
         vec_slot(e, p + "mlp.down_proj.bias", {vH}, L.down_b, 0.02, 0);
     }
     e->vlnq = falloc(e, vH);
     vec_slot(e, "visual.merger.ln_q.weight", {vH}, e->vlnq, 0.05, 1.0);
     e->m0_w = oalloc(e, (size_t)vHm * vHm); e->m0_b = falloc(e, vHm);
     e->m2_w = oalloc(e, (size_t)D * vHm); e->m2_b = falloc(e, D);
-    add_slot(e, "visual.merger.mlp.0.weight", {vHm, vHm}, e->m0_w, vHm, vHm, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, "visual.merger.mlp.0.weight", {vHm, vHm}, e->m0_w->hi, vHm, vHm, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, "visual.merger.mlp.0.bias", {vHm}, e->m0_b, 0.02, 0);
-    add_slot(e, "visual.merger.mlp.2.weight", {D, vHm}, e->m2_w, vHm, vHm, od, PACK_PLAIN, 0.02, 0);
+    add_slot(e, "visual.merger.mlp.2.weight", {D, vHm}, e->m2_w->hi, vHm, vHm, od, PACK_PLAIN, 0.02, 0);
     vec_slot(e, "visual.merger.mlp.2.bias", {D}, e->m2_b, 0.02, 0);
 
     e->dl.resize(d.layers);
@@ -129,17 +129,17 @@ void build_weight_table_qwen(lr_engine* e) {
         const int n[3] = {Hq, Hkv, Hkv}, off[3] = {0, Hq, Hq + Hkv};
         for (int i = 0; i < 3; ++i) {
             const int mode = i < 2 ? PACK_ROPE_QKV : PACK_PLAIN;
-            add_slot(e, p + "self_attn." + nm[i] + ".weight", {n[i], D}, (char*)L.qkv_w + (size_t)off[i] * D * 2, D, D, od, mode, 0.02, 0);
+            add_slot(e, p + "self_attn." + nm[i] + ".weight", {n[i], D}, L.qkv_w->hi + (size_t)off[i] * D * 2, D, D, od, mode, 0.02, 0);
             e->slots.back().aux_d = n[i]; e->slots.back().aux_hd = hd;
             add_slot(e, p + "self_attn." + nm[i] + ".bias", {n[i]}, L.qkv_b + off[i], 1, 1, DT_F32, mode, 0.02, 0);
             e->slots.back().rows = n[i]; e->slots.back().cols = 1;
             e->slots.back().aux_d = n[i]; e->slots.back().aux_hd = hd;
         }
-        add_slot(e, p + "self_attn.o_proj.weight", {D, Hq}, L.o_w, Hq, Hq, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "self_attn.o_proj.weight", {D, Hq}, L.o_w->hi, Hq, Hq, od, PACK_PLAIN, 0.02, 0);
         vec_slot(e, p + "post_attention_layernorm.weight", {D}, L.ln2, 0.05, 1.0);
-        add_slot(e, p + "mlp.gate_proj.weight", {I, D}, L.gu_w, D, D, od, PACK_SWIGLU_GATE, 0.02, 0);
-        add_slot(e, p + "mlp.up_proj.weight", {I, D}, L.gu_w, D, D, od, PACK_SWIGLU_UP, 0.02, 0);
-        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w, I, I, od, PACK_PLAIN, 0.02, 0);
+        add_slot(e, p + "mlp.gate_proj.weight", {I, D}, L.gu_w->hi, D, D, od, PACK_SWIGLU_GATE, 0.02, 0);
+        add_slot(e, p + "mlp.up_proj.weight", {I, D}, L.gu_w->hi, D, D, od, PACK_SWIGLU_UP, 0.02, 0);
+        add_slot(e, p + "mlp.down_proj.weight", {D, I}, L.down_w->hi, I, I, od, PACK_PLAIN, 0.02, 0);
         if (d.lora_rank > 0) {      // utils/utils.py:223-242 create_lora_config_qwen: q, k, v, o, gate, up, down of every decoder layer
             for (int i = 0; i < 3; ++i)
                 register_lora(e, L.lqkv, p + "self_attn." + nm[i], e->Nqkv, D, i, 3, n[i], off[i], i < 2 ? PACK_ROPE_QKV : PACK_PLAIN, n[i], hd);

@@ -927,6 +927,65 @@ def test_weight_reupload_after_finalize_rebuilds_e4m3_twins(dtype):
         assert (r2 - r0).abs().max().item() < TOL_X8
 
 
+def _strict_fwd(m, batch):
+    """The same handle with every stage in the strict form (16-bit residual passes), then back to the form it runs."""
+    m.engine.set_precision_map(1, 1)
+    r = _fwd(m, batch)
+    m._apply_form()
+    return r
+
+
+def test_resynthesis_makes_every_buffer_inexact_and_exact_again():
+    """lr_synth_weights_ex after lr_finalize, fp32-valued and back: every operand-weight buffer turns inexact (its e4m3 twin moves to
+    [e4m3(W) | e4m3(W_lo)] rows in a buffer of its own, the third e4m3 segment runs) and exact again (those rows are given back, the
+    twin returns to the rows of the residual buffer).  Parity against the oracle on the fp32-valued set; the way back is bit-exact."""
+    cfg = synth.tiny_config()
+    seed = 29
+    batch = synth.synth_batch(cfg, seed, [6, 4], [(1, 1), (1, 2)], max_crops=4)
+    m = _model(cfg, seed, "f16x2f8", upload=False, calibrate=False)
+    m.engine.set_gemm_tile(6)
+    r0 = _fwd(m, batch)
+    m.engine.synth_weights(seed, fp32_valued=True)
+    r1 = _fwd(m, batch)
+    W = orc.weights_to_torch(synth.make_weights(cfg, seed, synth.PROFILE_FP32))
+    # (the engine keeps the embedding table in bf16 whatever it is given -- it is no GEMM operand -- so the oracle gets it as stored;
+    #  with the table left fp32-valued the ORACLE moves by 3.8e-4 on these rows, and the engine sat 3.79e-4 from it before and after)
+    W["model.embed_tokens.weight"] = W["model.embed_tokens.weight"].to(torch.bfloat16).float()
+    ref = orc.custom_forward(W, cfg, batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["image_sizes"])
+    print(f"[resynth] fp32-valued: moved {(r1 - r0).abs().max().item():.2e}   err {(r1 - ref).abs().max().item():.2e}")
+    assert (r1 - r0).abs().max().item() > 1e-4                    # the new weights are in effect
+    assert (r1 - ref).abs().max().item() < TOL_X8
+    assert not torch.equal(r1, _strict_fwd(m, batch))             # the e4m3 forms ran
+    m.engine.synth_weights(seed)
+    r2 = _fwd(m, batch)
+    print(f"[resynth] back: |r2 - r0| = {(r2 - r0).abs().max().item():.2e}")
+    assert torch.equal(r2, r0)
+    assert not torch.equal(r2, _strict_fwd(m, batch))
+
+
+def test_w8a8_reupload_keeps_its_results():
+    """W8A8 mode: an upload marks the e4m3 twin of ITS weight stale; the twin is rebuilt in the buffers it already has.  A changed
+    weight is in effect at the next forward, and the original value uploaded again, three times over, gives the first forward's bits."""
+    cfg = synth.tiny_config()
+    seed = 29
+    batch = synth.synth_batch(cfg, seed, [6, 4], [(1, 1), (1, 2)], max_crops=4)
+    m = _model(cfg, seed, "fp8", upload=True)
+    m.engine.set_gemm_tile(6)
+    r0 = _fwd(m, batch)
+    strict = _model(cfg, seed, "f16x2", upload=True)
+    strict.engine.set_gemm_tile(6)
+    assert not torch.equal(r0, _fwd(strict, batch))               # the e4m3 GEMMs ran
+    name = "model.layers.1.mlp.down_proj.weight"
+    w = torch.from_numpy(synth.make_weights(cfg, seed)[name])
+    m.engine.upload(name, (w * (1.0 + 0.05 * torch.randn(w.shape, generator=torch.Generator().manual_seed(1)))).float())
+    moved = (_fwd(m, batch) - r0).abs().max().item()
+    print(f"[w8a8 re-upload] perturbed weight moves the reward by {moved:.2e}")
+    assert moved > 1e-4                                           # the new weight is in effect
+    for _ in range(3):
+        m.engine.upload(name, w)
+        assert torch.equal(_fwd(m, batch), r0)
+
+
 def test_su_rope_switch_point_of_the_flash_attention_class():
     """lr_model_desc.rope_flash_convention (RewardConfig.rope_flash_convention; set from the checkpoint's `_attn_implementation` or
     args.flash_attn).  Phi3FlashAttention2 calls the rotary module with max(S, position_ids[:, -1].max()) + 1 = S + 1

@@ -57,6 +57,55 @@ def test_llava_tiny_vs_oracle(dtype, tol, gpm):
         assert torch.equal(_fwd(m2, batch, rows=slice(b, b + 1))[0], got[b])
 
 
+def test_partial_upload_into_a_fused_buffer_after_finalize():
+    """k_proj uploaded after lr_finalize: a PART of the fused q|k|v buffer, whose e4m3 twin sits in the rows of its residual buffer.
+    bf16-valued: the buffer stays exact, its residual rows are zeroed again before the twin is rebuilt.  fp32-valued: the buffer turns
+    inexact, the twin moves to [e4m3(W) | e4m3(W_lo)] rows of its own.  The original again: a partial upload cannot clear the flag, so
+    the buffer keeps the inexact form with all-zero residuals.  Parity (3e-4) against the oracle on the substituted weight at every
+    step; the way back gives the first forward's value to parity, not to the bit."""
+    cfg = synth.llava_tiny_config()
+    seed = 21
+    tol = 3e-4                                                    # the default form's bound (tests/test_gpu_forward.py TOL_X8)
+    batch = synth.llava_synth_batch(cfg, seed, [6, 3], [(336, 336), (300, 500)])
+    Wn = synth.llava_make_weights(cfg, seed)
+    name = "language_model.model.layers.0.self_attn.k_proj.weight"
+    m = RewardModel(cfg, weights={k: torch.from_numpy(v) for k, v in Wn.items()}, max_batch=3, max_seq=4096, max_crops=5,
+                    operand_dtype="f16x2f8", calibrate=False).to("cuda").eval()
+    m.engine.set_gemm_tile(6)
+
+    def oracle(w):
+        W = orc.weights_to_torch(Wn)
+        W[name] = w
+        return lorc.custom_forward(W, cfg, batch["input_ids"], batch["attention_mask"], batch["pixel_values"], batch["image_sizes"])
+
+    def strict():
+        m.engine.set_precision_map(1, 1)
+        r = _fwd(m, batch)
+        m._apply_form()
+        return r
+
+    r0 = _fwd(m, batch)
+    assert not torch.equal(r0, strict())                          # the e4m3 forms run
+    w0 = torch.from_numpy(Wn[name])
+    w1 = torch.from_numpy(synth.llava_make_weights(cfg, seed + 1)[name])          # bf16-valued
+    w2 = (w1 * (1.0 + 0.05 * torch.randn(w1.shape, generator=torch.Generator().manual_seed(1)))).float()      # fp32-valued: inexact in f16
+    prev = r0
+    for tag, w in (("bf16-valued", w1), ("fp32-valued", w2)):
+        m.engine.upload(name, w)
+        r = _fwd(m, batch)
+        err, moved = (r - oracle(w)).abs().max().item(), (r - prev).abs().max().item()
+        print(f"[partial upload, {tag}] err {err:.2e}   moved {moved:.2e}")
+        assert moved > 1e-4                                       # the new weight is in effect
+        assert err < tol
+        assert not torch.equal(r, strict())
+        prev = r
+    m.engine.upload(name, w0)
+    r3 = _fwd(m, batch)
+    print(f"[partial upload, original again] |r3 - r0| = {(r3 - r0).abs().max().item():.2e}   equal {torch.equal(r3, r0)}")
+    assert (r3 - r0).abs().max().item() < tol
+    assert not torch.equal(r3, strict())
+
+
 CASES = sorted(glob.glob(os.path.join(GOLD, "ref_llava_*.json")))
 # every golden in both parity forms (full-size rows: several seeds, an outlier-bearing weight set, and the e4m3-VALUED weight set of
 # BASELINE configs[4] -- the reference run on the de-quantised weights of an fp8-weight checkpoint); the single-pass fast mode on the

@@ -118,6 +118,45 @@ def test_unmerged_adapter_fp32_valued(backbone, dtype):
         assert (gm - got).abs().max().item() < 1e-4
 
 
+def test_adapter_a_reuploaded_after_finalize():
+    """An adapter's A matrix uploaded after lr_finalize: its e4m3 twin lives in a buffer of its own and must be rebuilt at the next
+    launch.  Parity against the un-merged oracle on the substituted matrix; the original uploaded again gives the first forward's bits."""
+    seed = 31
+    cfg, Wn, batch, fwd = _case("phi3v", 16, seed)
+    name = "model.layers.1.self_attn.qkv_proj.lora_A.weight"
+    m = RewardModel(cfg, weights={k: torch.from_numpy(v) for k, v in Wn.items()}, max_batch=4, max_seq=1024, max_crops=5,
+                    operand_dtype="f16x2f8", calibrate=False).to("cuda").eval()
+    m.engine.set_gemm_tile(6)
+    tb = {k: torch.from_numpy(v).cuda() for k, v in batch.items()}
+
+    def run():
+        r, _ = m.custom_forward(tb["input_ids"], tb["attention_mask"], tb["pixel_values"], tb["image_sizes"])
+        torch.cuda.synchronize()
+        return r.cpu()
+
+    def strict():
+        m.engine.set_precision_map(1, 1)
+        r = run()
+        m._apply_form()
+        return r
+
+    r0 = run()
+    a1 = torch.from_numpy(synth.make_weights(cfg, seed + 1)[name])
+    m.engine.upload(name, a1)
+    r1 = run()
+    W = orc.weights_to_torch(Wn)
+    W[name] = a1
+    err, moved = (r1 - fwd(W)).abs().max().item(), (r1 - r0).abs().max().item()
+    print(f"[adapter A re-upload] err {err:.2e}   moved {moved:.2e}")
+    assert moved > 1e-4                                           # the new matrix is in effect
+    assert err < TOL["f16x2f8"]
+    assert not torch.equal(r1, strict())                          # the e4m3 forms ran
+    m.engine.upload(name, torch.from_numpy(Wn[name]))
+    r2 = run()
+    print(f"[adapter A re-upload] original again: |r2 - r0| = {(r2 - r0).abs().max().item():.2e}")
+    assert torch.equal(r2, r0)
+
+
 def test_loader_to_engine_phi3v(tmp_path):
     """load_reward_adaptor on a fabricated checkpoint directory -- bf16 safetensors base, pytorch_model.bin heads + ft_projector,
     PEFT adapter with `base_model.model.` prefix and the `.default.` adapter-name infix in adapter_model.safetensors --
