@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LR_ABI_VERSION 11
+#define LR_ABI_VERSION 12
 
 enum { LR_OK = 0, LR_EINVAL = 1, LR_EHIP = 2, LR_ESTATE = 3, LR_ENOTFOUND = 4, LR_ENOMEM = 5 };
 enum { LR_DT_BF16 = 0, LR_DT_F16 = 1, LR_DT_F32 = 2 };
@@ -352,6 +352,33 @@ int lr_op_rms_rows_f32(const float* x, const float* w, float eps, float* y, int 
 int lr_op_ca_softmax_pad(float* sc, int rows, int ld, int vb, int Vmax, void* hip_stream);
 int lr_op_ca_pool(const float* h, const float* o, const float* u, const float* ca_w, float ca_eps, const int64_t* mask, float* pooled,
                   int B, int S, int D, void* hip_stream);
+/* The integer plans, the RoPE tables and the RoPE fallback, one launch each (ABI 12; arguments as the launchers of csrc/kernels.h in the
+ * launchers' order, all pointers DEVICE).  token_plan: pos / img_row [B, S] int32, tstat [B][4]; image_token_id < 0: ids in (-1e9, 0)
+ * are image slots, >= 0: ids equal to it; pos_arange 1: pos = arange(S); mask NULL: every token valid; positions count from pos_base,
+ * slot ranks from *img_base (NULL: 0); voff_stride as below.  slot_check: rewards [B, d] get NaN where tstat[b][2] differs from row b's
+ * image-row count.  prefix_header: hdr[0..2] = {0, V, tstat[2]}.  embed: x [rows, D] fp32 = ev[img_row] or wte_bf16[clamp(id, 0,
+ * vocab - 1)] (D % 4 == 0, vocab >= 1).  rope_table: cs [B * S][half][2] = (cos, sin) * scaling, long factors iff
+ * (rotary_seq_len > 0 ? rotary_seq_len : S) > orig_max_pos.  rope_split: qkv32 [rows, rope_cols + v_cols] fp32 -> operand type
+ * ([hi | lo] when prec = 1), pairs (2i, 2i + 1) of every hd-wide head of the first rope_cols columns rotated by cs[row][i]
+ * (hd % 8 == 0, rope_cols % hd == 0, v_cols % 4 == 0).  qwen_plan: imgs int32 [n_images][4] = {merged grid h, w, advance, first slot},
+ * pos3 [3][B * S], rstat [B][4] = {image runs, tokens == ca_token, 0, 0}; S >= 1, mask required, n_images >= 1 and n_slots >= 1 when a
+ * table is passed.  mrope_table: s0, s1 >= 0, s0 + s1 <= half.  vit_rope_table: hw int32 [rows][2], 2 * quarter <= half_pad; pairs
+ * behind 2 * quarter are (1, 0).  qwen_ca_vec: out [B, D] = rstat[b][1] > 0 ? u : 0.  LR_EINVAL (nothing launched) otherwise. */
+int lr_op_token_plan(const int64_t* ids, const int64_t* mask, int B, int S, const int* voff, int* img_row, int* pos, int* tstat,
+                     long image_token_id, int pos_arange, int pos_base, const int* img_base, int voff_stride, void* hip_stream);
+int lr_op_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, int voff_stride, void* hip_stream);
+int lr_op_prefix_header(const int* tstat, int V, int* hdr, void* hip_stream);
+int lr_op_embed(const int64_t* ids, const int* img_row, const void* wte_bf16, const float* ev, float* x, int rows, int D, int vocab,
+                void* hip_stream);
+int lr_op_rope_table(const int* pos, const int* tstat, int B, int S, const float* inv_freq_short, const float* inv_freq_long, float scaling,
+                     int orig_max_pos, int half, float* cs, int rotary_seq_len, void* hip_stream);
+int lr_op_rope_split(const float* qkv32, const float* cs, void* out, int rows, int rope_cols, int v_cols, int hd, int operand_dtype, int prec,
+                     void* hip_stream);
+int lr_op_qwen_plan(const int64_t* ids, const int64_t* mask, int B, int S, long image_token, long ca_token, const int* imgs, int n_images,
+                    const int* slot2row, int n_slots, int* rstat, int* pos3, int* img_row, void* hip_stream);
+int lr_op_mrope_table(const int* pos3, int rows, const float* inv_freq, int s0, int s1, int half, float* cs, void* hip_stream);
+int lr_op_vit_rope_table(const int* hw, int rows, const float* inv_freq, int quarter, int half_pad, float* cs, void* hip_stream);
+int lr_op_qwen_ca_vec(const int* rstat, const float* u, int B, int D, float* out, void* hip_stream);
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std, float offset, int bf16_round,
                      void* hip_stream);
 

@@ -1158,6 +1158,51 @@ int lr_op_ca_pool(const float* h, const float* o, const float* u, const float* c
     return op_guard([&] { launch_ca_pool(h, o, u, ca_w, ca_eps, mask, pooled, B, S, D, (hipStream_t)hip_stream); });
 }
 
+int lr_op_token_plan(const int64_t* ids, const int64_t* mask, int B, int S, const int* voff, int* img_row, int* pos, int* tstat,
+                     long image_token_id, int pos_arange, int pos_base, const int* img_base, int voff_stride, void* hip_stream) {
+    return op_guard([&] { launch_token_plan(ids, mask, B, S, voff, img_row, pos, tstat, (hipStream_t)hip_stream, image_token_id, pos_arange, pos_base, img_base, voff_stride); });
+}
+
+int lr_op_slot_check(const int* tstat, const int* voff, float* rewards, int B, int d, int voff_stride, void* hip_stream) {
+    return op_guard([&] { launch_slot_check(tstat, voff, rewards, B, d, (hipStream_t)hip_stream, voff_stride); });
+}
+
+int lr_op_prefix_header(const int* tstat, int V, int* hdr, void* hip_stream) {
+    return op_guard([&] { launch_prefix_header(tstat, V, hdr, (hipStream_t)hip_stream); });
+}
+
+int lr_op_embed(const int64_t* ids, const int* img_row, const void* wte_bf16, const float* ev, float* x, int rows, int D, int vocab,
+                void* hip_stream) {
+    return op_guard([&] { launch_embed(ids, img_row, (const unsigned short*)wte_bf16, ev, x, rows, D, vocab, (hipStream_t)hip_stream); });
+}
+
+int lr_op_rope_table(const int* pos, const int* tstat, int B, int S, const float* inv_freq_short, const float* inv_freq_long, float scaling,
+                     int orig_max_pos, int half, float* cs, int rotary_seq_len, void* hip_stream) {
+    return op_guard([&] { launch_rope_table(pos, tstat, B, S, inv_freq_short, inv_freq_long, scaling, orig_max_pos, half, cs, (hipStream_t)hip_stream, rotary_seq_len); });
+}
+
+int lr_op_rope_split(const float* qkv32, const float* cs, void* out, int rows, int rope_cols, int v_cols, int hd, int operand_dtype, int prec,
+                     void* hip_stream) {
+    return op_guard([&] { launch_rope_split(qkv32, cs, out, rows, rope_cols, v_cols, hd, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec); });
+}
+
+int lr_op_qwen_plan(const int64_t* ids, const int64_t* mask, int B, int S, long image_token, long ca_token, const int* imgs, int n_images,
+                    const int* slot2row, int n_slots, int* rstat, int* pos3, int* img_row, void* hip_stream) {
+    return op_guard([&] { launch_qwen_plan(ids, mask, B, S, image_token, ca_token, (const int4*)imgs, n_images, slot2row, n_slots, rstat, pos3, img_row, (hipStream_t)hip_stream); });
+}
+
+int lr_op_mrope_table(const int* pos3, int rows, const float* inv_freq, int s0, int s1, int half, float* cs, void* hip_stream) {
+    return op_guard([&] { launch_mrope_table(pos3, rows, inv_freq, s0, s1, half, cs, (hipStream_t)hip_stream); });
+}
+
+int lr_op_vit_rope_table(const int* hw, int rows, const float* inv_freq, int quarter, int half_pad, float* cs, void* hip_stream) {
+    return op_guard([&] { launch_vit_rope_table((const int2*)hw, rows, inv_freq, quarter, half_pad, cs, (hipStream_t)hip_stream); });
+}
+
+int lr_op_qwen_ca_vec(const int* rstat, const float* u, int B, int D, float* out, void* hip_stream) {
+    return op_guard([&] { launch_qwen_ca_vec(rstat, u, B, D, out, (hipStream_t)hip_stream); });
+}
+
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std_, float offset, int bf16_round,
                      void* hip_stream) {
     return op_guard([&] { launch_synth_fill(out, n, tensor_seed(seed, name), uniform_scale(std_), offset, bf16_round, (hipStream_t)hip_stream); });

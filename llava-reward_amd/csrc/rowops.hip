@@ -367,6 +367,7 @@ __global__ __launch_bounds__(256) void token_plan_kernel(const int64_t* __restri
 void launch_token_plan(const int64_t* ids, const int64_t* mask, int B, int S, const int* voff, int* img_row, int* pos,
                        int* tstat, hipStream_t st, long image_token_id, int pos_arange, int pos_base, const int* img_base, int voff_stride) {
     if (B <= 0) return;
+    if (S < 1) throw std::runtime_error("token_plan: S must be at least 1");
     hipLaunchKernelGGL(token_plan_kernel, dim3(B), dim3(256), 0, st, ids, mask, S, voff, img_row, pos, tstat, image_token_id, pos_arange,
                        pos_base, img_base, voff_stride);
 }
@@ -421,6 +422,7 @@ __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ 
 void launch_embed(const int64_t* ids, const int* img_row, const unsigned short* wte_bf16, const float* ev, float* x,
                   int rows, int D, int vocab, hipStream_t st) {
     if (rows <= 0) return;
+    if (D % 4 || vocab < 1) throw std::runtime_error("embed: D must be a multiple of 4 and vocab at least 1");
     hipLaunchKernelGGL(embed_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, ids, img_row, wte_bf16, ev, x, rows, D, vocab);
 }
 

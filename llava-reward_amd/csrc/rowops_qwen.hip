@@ -74,6 +74,7 @@ __global__ __launch_bounds__(256) void vit_rope_table_kernel(const int2* __restr
 
 void launch_vit_rope_table(const int2* hw, int rows, const float* inv_freq, int quarter, int half_pad, float* cs, hipStream_t st) {
     if (rows <= 0) return;
+    if (quarter < 0 || 2 * quarter > half_pad) throw std::runtime_error("vit_rope_table: 2 * quarter must not exceed half_pad");
     hipLaunchKernelGGL(vit_rope_table_kernel, dim3(cdivq((long)rows * half_pad, 256)), dim3(256), 0, st, hw, rows, inv_freq, quarter, half_pad, cs);
 }
 
@@ -199,6 +200,10 @@ __global__ __launch_bounds__(64) void qwen_plan_kernel(const int64_t* __restrict
 void launch_qwen_plan(const int64_t* ids, const int64_t* mask, int B, int S, long image_token, long ca_token, const int4* imgs,
                       int n_images, const int* slot2row, int n_slots, int* rstat, int* pos3, int* img_row, hipStream_t st) {
     if (B <= 0) return;
+    if (S < 1) throw std::runtime_error("qwen_plan: S must be at least 1");
+    if (!mask) throw std::runtime_error("qwen_plan: the attention mask is required");                  // qwen_runs_kernel reads it unconditionally
+    if ((imgs || slot2row) && (n_images < 1 || n_slots < 1))                                            // the clamps min(.., n - 1) need n >= 1
+        throw std::runtime_error("qwen_plan: image tables need n_images >= 1 and n_slots >= 1");
     hipLaunchKernelGGL(qwen_runs_kernel, dim3(B), dim3(64), 0, st, ids, mask, S, image_token, ca_token, rstat);
     hipLaunchKernelGGL(qwen_plan_kernel, dim3(B), dim3(64), 0, st, ids, mask, B, S, image_token, rstat, imgs, n_images, slot2row,
                        n_slots, pos3, img_row);
@@ -220,6 +225,7 @@ __global__ __launch_bounds__(256) void mrope_table_kernel(const int* __restrict_
 
 void launch_mrope_table(const int* pos3, int rows, const float* inv_freq, int s0, int s1, int half, float* cs, hipStream_t st) {
     if (rows <= 0) return;
+    if (s0 < 0 || s1 < 0 || s0 + s1 > half) throw std::runtime_error("mrope_table: sections must be non-negative and s0 + s1 <= half");
     hipLaunchKernelGGL(mrope_table_kernel, dim3(cdivq((long)rows * half, 256)), dim3(256), 0, st, pos3, rows, inv_freq, s0, s1, half, cs);
 }
 
