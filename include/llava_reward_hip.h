@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LR_ABI_VERSION 12
+#define LR_ABI_VERSION 13
 
 enum { LR_OK = 0, LR_EINVAL = 1, LR_EHIP = 2, LR_ESTATE = 3, LR_ENOTFOUND = 4, LR_ENOMEM = 5 };
 enum { LR_DT_BF16 = 0, LR_DT_F16 = 1, LR_DT_F32 = 2 };
@@ -381,6 +381,38 @@ int lr_op_vit_rope_table(const int* hw, int rows, const float* inv_freq, int qua
 int lr_op_qwen_ca_vec(const int* rstat, const float* u, int B, int D, float* out, void* hip_stream);
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std, float offset, int bf16_round,
                      void* hip_stream);
+/* The vision operand producers and gathers, one launch each (ABI 13; arguments as the launchers of csrc/kernels.h, all pointers DEVICE;
+ * pix_dtype LR_DT_F32 or LR_DT_BF16; prec = 1: [hi | lo] rows).  im2col: pixels [*, 3, img, img], out row (crop, py, px) = patch of crop
+ * crop_src[crop], column c * patch^2 + ky * patch + kx, zero up to Kpad (patch >= 1, img % patch == 0, Kpad >= 3 patch^2).  clip_embed:
+ * x [ncrop * T, H] = LayerNorm(t == 0 ? cls : patch_out[crop * (T - 1) + t - 1], + pos[t]) (H % 4 == 0, H <= 4096, T >= 2).  hd_gather:
+ * samples int32 [B][4] = {hc, wc, first crop, first output row}; out [total_rows, 4 H] = the Phi-3-V HD transform of clipx [*, T, H]
+ * (H % 4 == 0, T = g^2 + 1 with g even, B >= 1).  clip_tokens: out [ncrop * (T - 1), H] = clipx without the CLS rows (H % 4 == 0,
+ * T >= 2).  llava_pack: samples int32 [B][8] = {gh, gw, r0, r1, c0, c1, first crop, first output row}; ev [total_rows, D] = base crop,
+ * then rows r0..r1 x columns c0..c1 of the crop grid with `newline` behind every row (D % 4 == 0, g >= 1, B >= 1).  qwen_patch_gather:
+ * out row i = pixels row src[i] of K values, zero up to Kpad (Kpad % 4 == 0, Kpad >= K).  LR_EINVAL (nothing launched) otherwise. */
+int lr_op_im2col(const void* pixels, int pix_dtype, const int* crop_src, int ncrop, int img, int patch, int Kpad, void* out,
+                 int operand_dtype, int prec, void* hip_stream);
+int lr_op_clip_embed(const float* patch_out, const float* cls, const float* pos, const float* lnw, const float* lnb, float* x, int ncrop,
+                     int T, int H, float eps, void* hip_stream);
+int lr_op_hd_gather(const float* clipx, const int* samples, int B, int total_rows, int T, int H, const float* sub_gn, const float* glb_gn,
+                    void* out, int operand_dtype, int prec, void* hip_stream);
+int lr_op_clip_tokens(const float* clipx, void* out, int ncrop, int T, int H, int operand_dtype, int prec, void* hip_stream);
+int lr_op_llava_pack(const float* proj, const int* samples, int B, int total_rows, int g, int D, const float* newline, float* ev,
+                     void* hip_stream);
+int lr_op_qwen_patch_gather(const void* pixels, int pix_dtype, const int* src, int rows, int K, int Kpad, void* out, int operand_dtype,
+                            int prec, void* hip_stream);
+/* Host only (no handle, no device; ABI 13): the plans the forwards compute on the host, from the code the forwards run.
+ * lr_vision_sample_plan: one image of size (height, width) under LR_BACKBONE_PHI3V (pinpoints ignored) or LR_BACKBONE_LLAVA_NEXT
+ * (pinpoints HOST int32 [n][2] = (h, w), multiples of crop); crop = crop side in pixels, g = CLIP grid side.  sample = the 4 (Phi-3-V) or
+ * 8 (LLaVA) ints lr_op_hd_gather / lr_op_llava_pack take, first crop and first output row 0; *n_crops, *n_rows = crops and image rows.
+ * lr_qwen_vision_plan: grid_thw HOST int64 [n_images][3]; window side in merged tokens = window / merge / patch.  Fills src [N],
+ * hw [N][2], slot2row [N / merge^2], items_win / items_full [..][4] = {first row, length, 128-query tile, 0}, imgs [n_images][4] and
+ * counts = {N, nwin, nfull, max_seg}; the arrays hold capacity_patches, 2 capacity_patches, capacity_patches / merge^2,
+ * 4 capacity_patches / merge^2, 4 (capacity_patches / 128 + n_images) and 4 n_images ints. */
+int lr_vision_sample_plan(int backbone, int crop, int g, const int32_t* pinpoints, int n_pinpoints, int64_t height, int64_t width,
+                          int32_t* sample, int32_t* n_crops, int32_t* n_rows);
+int lr_qwen_vision_plan(const int64_t* grid_thw, int n_images, int merge, int window, int patch, int capacity_patches, int32_t* src,
+                        int32_t* hw, int32_t* slot2row, int32_t* items_win, int32_t* items_full, int32_t* imgs, int32_t* counts);
 
 /* ---- input hand-over: the Phi-3.5-V image processor on the GPU ----
  * Replaces Phi3VImageProcessor.preprocess (llava_reward/models/base_mllm/phi3_v/processing_phi3_v.py:262-288 with

@@ -315,29 +315,30 @@ void run_mean_pool_head(lr_engine* h, hipStream_t st, const int64_t* attention_m
 }
 
 // Host plan of one sample's image (h, w = hh, ww; its first crop NC and first image row SV): fills the sample's table entry and
-// returns its crop and image-row counts.  Phi-3-V: the HD crop grid, modeling_phi3_v.py:276-297.
+// returns its crop and image-row counts.  The few config values arrive as arguments (img = crop side in pixels, G = CLIP grid side), so
+// that lr_vision_sample_plan runs the same code without a handle.  Phi-3-V: the HD crop grid, modeling_phi3_v.py:276-297.
 struct SamplePlan { int ncr, V; };
-static SamplePlan plan_hd_sample(const lr_engine* h, int64_t hh, int64_t ww, int NC, int SV, HdSample& smp, const char* who) {
-    const int img = h->d.clip_image, g2 = h->G / 2;
+static SamplePlan plan_hd_sample(int img, int G, int64_t hh, int64_t ww, int NC, int SV, HdSample& smp, const char* who) {
+    const int g2 = G / 2;
     if (hh <= 0 || ww <= 0 || hh % img || ww % img) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive multiples of the crop size");
     const int hc = (int)(hh / img), wc = (int)(ww / img);
     smp = HdSample{hc, wc, NC, SV};
     return {hc * wc + 1, hc * g2 * (wc * g2 + 1) + 1 + g2 * (g2 + 1)};
 }
 // LLaVA: anyres + unpad, modeling_llava_next.py:41-146,265-335
-static SamplePlan plan_llava_sample(const lr_engine* h, int64_t hh, int64_t ww, int NC, int SV, LlavaSample& smp, const char* who) {
-    const lr_model_desc& d = h->d;
+static SamplePlan plan_llava_sample(int img, int G, const int* pinpoints, int n_pinpoints, int64_t hh, int64_t ww, int NC, int SV,
+                                    LlavaSample& smp, const char* who) {
     if (hh <= 0 || ww <= 0) throw std::invalid_argument(std::string(who) + ": image_sizes must be positive");
     // transformers select_best_resolution: max effective resolution, then min waste
     long best_eff = 0, best_waste = 0; int bh = 0, bw = 0;
-    for (int i = 0; i < d.n_pinpoints; ++i) {
-        const int ph = d.pinpoints[2 * i], pw = d.pinpoints[2 * i + 1];
+    for (int i = 0; i < n_pinpoints; ++i) {
+        const int ph = pinpoints[2 * i], pw = pinpoints[2 * i + 1];
         const double sc = std::min((double)pw / (double)ww, (double)ph / (double)hh);
         const long dw = (long)((double)ww * sc), dh = (long)((double)hh * sc);
         const long eff = std::min(dw * dh, (long)(ww * hh)), waste = (long)pw * ph - eff;
         if (eff > best_eff || (eff == best_eff && (bh == 0 || waste < best_waste))) { best_eff = eff; best_waste = waste; bh = ph; bw = pw; }
     }
-    const int gh = bh / d.clip_image, gw = bw / d.clip_image, ch = gh * h->G, cw = gw * h->G;
+    const int gh = bh / img, gw = bw / img, ch = gh * G, cw = gw * G;
     int r0 = 0, r1 = ch, c0 = 0, c1 = cw;
     // unpad_image (modeling_llava_next.py:109-146): new extent = int(round(x, 7)) -- 7 decimals, then truncation
     auto trunc7 = [](double x) { return (int)(std::round(x * 1e7) / 1e7); };
@@ -347,7 +348,7 @@ static SamplePlan plan_llava_sample(const lr_engine* h, int64_t hh, int64_t ww, 
         const int pad = (cw - trunc7((double)ww * ((double)ch / (double)hh))) / 2; c0 = pad; c1 = cw - pad;
     }
     smp = LlavaSample{gh, gw, r0, r1, c0, c1, NC, SV};
-    return {1 + gh * gw, h->G * h->G + (r1 - r0) * (c1 - c0 + 1)};
+    return {1 + gh * gw, G * G + (r1 - r0) * (c1 - c0 + 1)};
 }
 
 // The image side of a pass, shared by lr_forward and lr_prefix_build: host plan (active crops, per-sample vision geometry, image-token
@@ -367,8 +368,8 @@ static VisionPlan run_vision(lr_engine* h, hipStream_t st, const void* pixel_val
     int NC = 0, SV = 0, Vmax = 0;
     for (int b = 0; b < B; ++b) {
         const int64_t hh = image_sizes_host[2 * b], ww = image_sizes_host[2 * b + 1];
-        const SamplePlan sp = h->llava ? plan_llava_sample(h, hh, ww, NC, SV, ((LlavaSample*)(th + smp_off))[b], who)
-                                       : plan_hd_sample(h, hh, ww, NC, SV, ((HdSample*)(th + smp_off))[b], who);
+        const SamplePlan sp = h->llava ? plan_llava_sample(d.clip_image, h->G, d.pinpoints, d.n_pinpoints, hh, ww, NC, SV, ((LlavaSample*)(th + smp_off))[b], who)
+                                       : plan_hd_sample(d.clip_image, h->G, hh, ww, NC, SV, ((HdSample*)(th + smp_off))[b], who);
         if (sp.ncr > n_crops) throw std::invalid_argument(std::string(who) + ": image_sizes needs more crops than pixel_values holds");
         voff[b] = SV;
         for (int c = 0; c < sp.ncr; ++c) crop_src[NC++] = b * n_crops + c;
@@ -1206,6 +1207,71 @@ int lr_op_qwen_ca_vec(const int* rstat, const float* u, int B, int D, float* out
 int lr_op_synth_fill(float* out, size_t n, uint64_t seed, const char* name, float std_, float offset, int bf16_round,
                      void* hip_stream) {
     return op_guard([&] { launch_synth_fill(out, n, tensor_seed(seed, name), uniform_scale(std_), offset, bf16_round, (hipStream_t)hip_stream); });
+}
+
+// ---- the vision operand producers and gathers (ABI 13): which pixel or CLIP feature lands in which operand row ----
+int lr_op_im2col(const void* pixels, int pix_dtype, const int* crop_src, int ncrop, int img, int patch, int Kpad, void* out,
+                 int operand_dtype, int prec, void* hip_stream) {
+    return op_guard([&] {
+        check_pix_dtype(pix_dtype, "lr_op_im2col");
+        launch_im2col(pixels, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, crop_src, ncrop, img, patch, Kpad, out, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec);
+    });
+}
+
+int lr_op_clip_embed(const float* patch_out, const float* cls, const float* pos, const float* lnw, const float* lnb, float* x, int ncrop,
+                     int T, int H, float eps, void* hip_stream) {
+    return op_guard([&] { launch_clip_embed(patch_out, cls, pos, lnw, lnb, x, ncrop, T, H, eps, (hipStream_t)hip_stream); });
+}
+
+int lr_op_hd_gather(const float* clipx, const int* samples, int B, int total_rows, int T, int H, const float* sub_gn, const float* glb_gn,
+                    void* out, int operand_dtype, int prec, void* hip_stream) {
+    static_assert(sizeof(HdSample) == 4 * sizeof(int), "HdSample crosses the ABI as 4 ints");
+    return op_guard([&] { launch_hd_gather(clipx, (const HdSample*)samples, B, total_rows, T, H, sub_gn, glb_gn, out, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec); });
+}
+
+int lr_op_clip_tokens(const float* clipx, void* out, int ncrop, int T, int H, int operand_dtype, int prec, void* hip_stream) {
+    return op_guard([&] { launch_clip_tokens(clipx, out, ncrop, T, H, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec); });
+}
+
+int lr_op_llava_pack(const float* proj, const int* samples, int B, int total_rows, int g, int D, const float* newline, float* ev,
+                     void* hip_stream) {
+    static_assert(sizeof(LlavaSample) == 8 * sizeof(int), "LlavaSample crosses the ABI as 8 ints");
+    return op_guard([&] { launch_llava_pack(proj, (const LlavaSample*)samples, B, total_rows, g, D, newline, ev, (hipStream_t)hip_stream); });
+}
+
+int lr_op_qwen_patch_gather(const void* pixels, int pix_dtype, const int* src, int rows, int K, int Kpad, void* out, int operand_dtype,
+                            int prec, void* hip_stream) {
+    return op_guard([&] {
+        check_pix_dtype(pix_dtype, "lr_op_qwen_patch_gather");
+        launch_qwen_patch_gather(pixels, pix_dtype == LR_DT_F32 ? DT_F32 : DT_BF16, src, rows, K, Kpad, out, op_dtype(operand_dtype), (hipStream_t)hip_stream, prec);
+    });
+}
+
+// Host only: the per-sample vision plan run_vision computes for one image (plan_hd_sample / plan_llava_sample), without a handle.
+int lr_vision_sample_plan(int backbone, int crop, int g, const int32_t* pinpoints, int n_pinpoints, int64_t height, int64_t width,
+                          int32_t* sample, int32_t* n_crops, int32_t* n_rows) {
+    return guarded(nullptr, [&] {
+        const char* who = "lr_vision_sample_plan";
+        if (!sample || !n_crops || !n_rows) throw std::invalid_argument(std::string(who) + ": null argument");
+        if (crop < 1 || g < 1) throw std::invalid_argument(std::string(who) + ": crop and g must be positive");
+        SamplePlan sp;
+        if (backbone == LR_BACKBONE_PHI3V) {
+            if (g % 2) throw std::invalid_argument(std::string(who) + ": the HD transform needs an even CLIP grid");
+            HdSample s;
+            sp = plan_hd_sample(crop, g, height, width, 0, 0, s, who);
+            std::memcpy(sample, &s, sizeof(s));
+        } else if (backbone == LR_BACKBONE_LLAVA_NEXT) {
+            if (!pinpoints || n_pinpoints < 1 || n_pinpoints > LR_MAX_PINPOINTS) throw std::invalid_argument(std::string(who) + ": n_pinpoints out of range");
+            for (int i = 0; i < 2 * n_pinpoints; ++i)
+                if (pinpoints[i] < crop || pinpoints[i] % crop) throw std::invalid_argument(std::string(who) + ": pinpoints must be positive multiples of the crop size");
+            LlavaSample s;
+            sp = plan_llava_sample(crop, g, pinpoints, n_pinpoints, height, width, 0, 0, s, who);
+            std::memcpy(sample, &s, sizeof(s));
+        } else {
+            throw std::invalid_argument(std::string(who) + ": backbone must be LR_BACKBONE_PHI3V or LR_BACKBONE_LLAVA_NEXT");
+        }
+        *n_crops = sp.ncr; *n_rows = sp.V;
+    });
 }
 
 }  // extern "C"

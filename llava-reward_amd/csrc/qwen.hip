@@ -34,6 +34,61 @@ QwenTables qwen_table_layout(const lr_model_desc& d) {
     return t;
 }
 
+// image_grid_thw as lr_forward_qwen accepts it; returns the patch count.
+long qwen_check_grids(const int64_t* grid_thw, int n_images, int m, const char* who) {
+    const std::string w = who;
+    long P = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const int64_t t = grid_thw[3 * i], gh = grid_thw[3 * i + 1], gw = grid_thw[3 * i + 2];
+        if (t != 1) throw std::invalid_argument(w + ": image_grid_thw[:, 0] must be 1 (video grids are out of scope)");
+        if (gh < m || gw < m || gh % m || gw % m) throw std::invalid_argument(w + ": grid h, w must be positive multiples of the merge size");
+        if (gh * gw > 8192) throw std::invalid_argument(w + ": more than 8192 patches per image are not supported");
+        P += gh * gw;
+    }
+    return P;
+}
+
+// The vision plan of one call (transformers.vision_utils get_vision_window_index / get_vision_position_ids / cu_seqlens) for grids
+// qwen_check_grids accepted: src / hw [N] (window order), slot2row [N / unit], the attention work items of the windowed and of the full
+// layers, imgs [n_images].  lr_forward_qwen and lr_qwen_vision_plan run this one copy.
+struct QwenPlanCounts { int N, nwin, nfull, max_seg; };
+QwenPlanCounts qwen_vision_plan(const int64_t* grid_thw, int n_images, int m, int ws, int unit, int* src, int2* hw, int* slot2row,
+                                int4* items_win, int4* items_full, int4* imgs) {
+    int nwin = 0, nfull = 0, row = 0, mbase = 0, max_seg = 0;
+    for (int i = 0; i < n_images; ++i) {
+        const int gh = (int)grid_thw[3 * i + 1], gw = (int)grid_thw[3 * i + 2];
+        const int lh = gh / m, lw = gw / m;
+        imgs[i] = make_int4(lh, lw, std::max(gh, gw) / m, mbase);
+        const int row_img = row;
+        // windows in row-major order of the (padded) window grid; a full extra window when the grid divides evenly
+        // stays empty, as in the reference
+        const int nh = (lh + (ws - lh % ws)) / ws, nw = (lw + (ws - lw % ws)) / ws;
+        for (int wy = 0; wy < nh; ++wy)
+            for (int wx = 0; wx < nw; ++wx) {
+                const int row0 = row;
+                for (int y = wy * ws; y < std::min(lh, (wy + 1) * ws); ++y)
+                    for (int x = wx * ws; x < std::min(lw, (wx + 1) * ws); ++x) {
+                        const int u = y * lw + x;                       // merge unit (processor order) of this image
+                        slot2row[mbase + u] = row / unit;
+                        for (int k = 0; k < unit; ++k) {
+                            // processor patch order inside the image: [lh, lw, m, m]
+                            src[row] = (mbase + u) * unit + k;
+                            hw[row] = make_int2(y * m + k / m, x * m + k % m);
+                            ++row;
+                        }
+                    }
+                const int len = row - row0;
+                for (int q = 0; q * 128 < len; ++q) items_win[nwin++] = make_int4(row0, len, q, 0);
+                max_seg = std::max(max_seg, len);
+            }
+        const int len = row - row_img;
+        for (int q = 0; q * 128 < len; ++q) items_full[nfull++] = make_int4(row_img, len, q, 0);
+        max_seg = std::max(max_seg, len);
+        mbase += lh * lw;
+    }
+    return QwenPlanCounts{row, nwin, nfull, max_seg};
+}
+
 }  // namespace
 
 void validate_desc_qwen(const lr_model_desc& d) {
@@ -255,48 +310,10 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         int4* items_full = (int4*)(th + T.items_full);
         int4* imgs = (int4*)(th + T.imgs);
         const int ws = d.vit_window / m / d.vit_patch;           // window side in merged tokens
-        long P = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const int64_t t = grid_thw[3 * i], gh = grid_thw[3 * i + 1], gw = grid_thw[3 * i + 2];
-            if (t != 1) throw std::invalid_argument("lr_forward_qwen: image_grid_thw[:, 0] must be 1 (video grids are out of scope)");
-            if (gh < m || gw < m || gh % m || gw % m) throw std::invalid_argument("lr_forward_qwen: grid h, w must be positive multiples of the merge size");
-            if (gh * gw > 8192) throw std::invalid_argument("lr_forward_qwen: more than 8192 patches per image are not supported");
-            P += gh * gw;
-        }
+        const long P = qwen_check_grids(grid_thw, n_images, m, "lr_forward_qwen");
         if (P > d.max_patches) throw std::invalid_argument("lr_forward_qwen: pixel_values has more patches than max_patches");
-        const int N = (int)P, M = N / unit;
-        int nwin = 0, nfull = 0, row = 0, mbase = 0, max_seg = 0;
-        for (int i = 0; i < n_images; ++i) {
-            const int gh = (int)grid_thw[3 * i + 1], gw = (int)grid_thw[3 * i + 2];
-            const int lh = gh / m, lw = gw / m;
-            imgs[i] = make_int4(lh, lw, std::max(gh, gw) / m, mbase);
-            const int row_img = row;
-            // windows in row-major order of the (padded) window grid; a full extra window when the grid divides evenly
-            // stays empty, as in the reference
-            const int nh = (lh + (ws - lh % ws)) / ws, nw = (lw + (ws - lw % ws)) / ws;
-            for (int wy = 0; wy < nh; ++wy)
-                for (int wx = 0; wx < nw; ++wx) {
-                    const int row0 = row;
-                    for (int y = wy * ws; y < std::min(lh, (wy + 1) * ws); ++y)
-                        for (int x = wx * ws; x < std::min(lw, (wx + 1) * ws); ++x) {
-                            const int u = y * lw + x;                       // merge unit (processor order) of this image
-                            slot2row[mbase + u] = row / unit;
-                            for (int k = 0; k < unit; ++k) {
-                                // processor patch order inside the image: [lh, lw, m, m]
-                                src[row] = (mbase + u) * unit + k;
-                                hw[row] = make_int2(y * m + k / m, x * m + k % m);
-                                ++row;
-                            }
-                        }
-                    const int len = row - row0;
-                    for (int q = 0; q * 128 < len; ++q) items_win[nwin++] = make_int4(row0, len, q, 0);
-                    max_seg = std::max(max_seg, len);
-                }
-            const int len = row - row_img;
-            for (int q = 0; q * 128 < len; ++q) items_full[nfull++] = make_int4(row_img, len, q, 0);
-            max_seg = std::max(max_seg, len);
-            mbase += lh * lw;
-        }
+        const QwenPlanCounts pc = qwen_vision_plan(grid_thw, n_images, m, ws, unit, src, hw, slot2row, items_win, items_full, imgs);
+        const int N = pc.N, M = N / unit, nwin = pc.nwin, nfull = pc.nfull, max_seg = pc.max_seg;
         tab.commit(st);
         const int* d_src = (const int*)(td + T.src);
         const int2* d_hw = (const int2*)(td + T.hw);
@@ -366,5 +383,31 @@ extern "C" int lr_forward_qwen(lr_handle h, const int64_t* input_ids, const int6
         }
         launch_reward_head(h->hL, ao, h->ca_w, d.ca_eps, h->vh, d.value_head_dim, rewards_out, B, D, st);
         LR_HIP_CHECK(hipGetLastError());
+    });
+}
+
+// Host only: the vision plan lr_forward_qwen computes for image_grid_thw (qwen_vision_plan), without a handle.
+extern "C" int lr_qwen_vision_plan(const int64_t* grid_thw, int n_images, int merge, int window, int patch, int capacity_patches,
+                                   int32_t* src, int32_t* hw, int32_t* slot2row, int32_t* items_win, int32_t* items_full, int32_t* imgs,
+                                   int32_t* counts) {
+    return guarded(nullptr, [&] {
+        const char* who = "lr_qwen_vision_plan";
+        if (!grid_thw || !src || !hw || !slot2row || !items_win || !items_full || !imgs || !counts) throw std::invalid_argument(std::string(who) + ": null argument");
+        if (n_images < 1) throw std::invalid_argument(std::string(who) + ": n_images must be positive");
+        if (merge < 1 || merge * merge > 128 || patch < 1 || window / merge / patch < 1)
+            throw std::invalid_argument(std::string(who) + ": merge in [1, 11], patch >= 1 and a window of at least one merged token");
+        const long P = qwen_check_grids(grid_thw, n_images, merge, who);
+        if (P > capacity_patches) throw std::invalid_argument(std::string(who) + ": the grids hold more patches than capacity_patches");
+        // (the callers' int32 arrays need not have the alignment of int2 / int4)
+        const size_t unit = (size_t)merge * merge, M = (size_t)P / unit;
+        std::vector<int2> hw2((size_t)P);
+        std::vector<int4> iw(M), ifull((size_t)P / 128 + n_images), im(n_images);
+        const QwenPlanCounts pc = qwen_vision_plan(grid_thw, n_images, merge, window / merge / patch, (int)unit, src, hw2.data(), slot2row,
+                                                   iw.data(), ifull.data(), im.data());
+        std::memcpy(hw, hw2.data(), (size_t)P * sizeof(int2));
+        std::memcpy(items_win, iw.data(), (size_t)pc.nwin * sizeof(int4));
+        std::memcpy(items_full, ifull.data(), (size_t)pc.nfull * sizeof(int4));
+        std::memcpy(imgs, im.data(), (size_t)n_images * sizeof(int4));
+        counts[0] = pc.N; counts[1] = pc.nwin; counts[2] = pc.nfull; counts[3] = pc.max_seg;
     });
 }

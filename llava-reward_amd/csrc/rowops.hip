@@ -241,6 +241,8 @@ __global__ __launch_bounds__(256) void im2col_kernel(const PT* __restrict__ pix,
 void launch_im2col(const void* pixels, int pix_dtype, const int* crop_src, int ncrop, int img, int patch, int Kpad,
                    void* out, int operand_dtype, hipStream_t st, int prec) {
     if (ncrop <= 0) return;
+    if (patch < 1 || img % patch || Kpad < 3 * patch * patch)      // (the kernel writes Kpad columns per patch row and would cut a longer patch short)
+        throw std::runtime_error("im2col: patch >= 1, img % patch == 0 and Kpad >= 3 * patch * patch are required");
     dim3 g(ncrop * (img / patch)), t(256);
     const bool f16 = operand_dtype == DT_F16;
     if (pix_dtype == DT_F32) {
@@ -303,7 +305,9 @@ __global__ __launch_bounds__(256) void clip_embed_kernel(const float* __restrict
 void launch_clip_embed(const float* patch_out, const float* cls, const float* pos, const float* lnw, const float* lnb,
                        float* x, int ncrop, int T, int H, float eps, hipStream_t st) {
     const int rows = ncrop * T;
-    if (rows <= 0) return;
+    if (ncrop <= 0) return;
+    if (H % 4 || H > 4 * 64 * NORM_MAXC || T < 2)                  // (float4 chunks, NORM_MAXC of them per lane; a CLS row and at least one patch row)
+        throw std::runtime_error("clip_embed: H % 4 == 0, H <= 4096 and T >= 2 are required");
     hipLaunchKernelGGL(clip_embed_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, patch_out, cls, pos, lnw, lnb, x, rows, T, H, eps);
 }
 
@@ -544,6 +548,8 @@ void launch_hd_gather(const float* clipx, const HdSample* samples, int B, int to
     if (total_rows <= 0) return;
     int g = 1;
     while (g * g + 1 < T) ++g;
+    if (H % 4 || g * g + 1 != T || g % 2 || B < 1)                 // (a float4 chunk must not straddle two of the four H-blocks)
+        throw std::runtime_error("hd_gather: H % 4 == 0, T == g * g + 1 with g even and B >= 1 are required");
     dim3 gr(cdiv(total_rows, 4)), t(256);
     if (operand_dtype == DT_F16) hipLaunchKernelGGL((hd_gather_kernel<F16>), gr, t, 0, st, clipx, samples, B, total_rows, T, H, g, sub_gn, glb_gn, out, prec);
     else hipLaunchKernelGGL((hd_gather_kernel<BF16>), gr, t, 0, st, clipx, samples, B, total_rows, T, H, g, sub_gn, glb_gn, out, prec);
@@ -565,7 +571,9 @@ __global__ __launch_bounds__(256) void clip_tokens_kernel(const float* __restric
 
 void launch_clip_tokens(const float* clipx, void* out, int ncrop, int T, int H, int operand_dtype, hipStream_t st, int prec) {
     const int rows = ncrop * (T - 1);
+    if (ncrop > 0 && T < 2) throw std::runtime_error("clip_tokens: T >= 2 is required");
     if (rows <= 0) return;
+    if (H % 4) throw std::runtime_error("clip_tokens: H % 4 == 0 is required");
     if (operand_dtype == DT_F16) hipLaunchKernelGGL((clip_tokens_kernel<F16>), dim3(cdiv(rows, 4)), dim3(256), 0, st, clipx, out, rows, T, H, prec);
     else hipLaunchKernelGGL((clip_tokens_kernel<BF16>), dim3(cdiv(rows, 4)), dim3(256), 0, st, clipx, out, rows, T, H, prec);
 }
@@ -601,6 +609,7 @@ __global__ __launch_bounds__(256) void llava_pack_kernel(const float* __restrict
 void launch_llava_pack(const float* proj, const LlavaSample* samples, int B, int total_rows, int g, int D,
                        const float* newline, float* ev, hipStream_t st) {
     if (total_rows <= 0) return;
+    if (D % 4 || g < 1 || B < 1) throw std::runtime_error("llava_pack: D % 4 == 0, g >= 1 and B >= 1 are required");
     hipLaunchKernelGGL(llava_pack_kernel, dim3(cdiv(total_rows, 4)), dim3(256), 0, st, proj, samples, B, total_rows, g, D, newline, ev);
 }
 

@@ -14,7 +14,7 @@ LR_MAX_HALF_HEAD = 64
 LR_MAX_PINPOINTS = 8
 LR_MAX_FULLATT = 8
 LR_BACKBONE_PHI3V, LR_BACKBONE_LLAVA_NEXT, LR_BACKBONE_QWEN2_5_VL = 0, 1, 2
-LR_ABI_VERSION = 12
+LR_ABI_VERSION = 13
 EPI_OUT_OP, EPI_OUT_F32, EPI_RESADD_F32, EPI_SWIGLU_OP, EPI_ROPE_OP = 0, 1, 2, 3, 4
 ACT_NONE, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2
 
@@ -132,6 +132,14 @@ _SIGS = {
     "lr_op_vit_rope_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lr_op_qwen_ca_vec": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "lr_op_synth_fill": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p, C.c_float, C.c_float, C.c_int, C.c_void_p]),
+    "lr_op_im2col": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lr_op_clip_embed": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "lr_op_hd_gather": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p]),
+    "lr_op_clip_tokens": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "lr_op_llava_pack": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
+    "lr_op_qwen_patch_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "lr_vision_sample_plan": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int32), C.c_int, C.c_int64, C.c_int64] + [C.POINTER(C.c_int32)] * 3),
+    "lr_qwen_vision_plan": (C.c_int, [C.POINTER(C.c_int64)] + [C.c_int] * 5 + [C.POINTER(C.c_int32)] * 7),
     "lr_hd_transform_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "lr_qwen_image_grid": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     "lr_qwen_image_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int64, C.c_int64]),

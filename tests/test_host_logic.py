@@ -19,14 +19,14 @@ from llava_reward_amd.scoring import gather_rewards, score_pairwise, score_singl
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_symbols_are_exported_at_abi_12():
-    """Every declared symbol resolves, and the library and the loader agree on ABI 12 (12: the single-kernel entries of the plan, RoPE
-    table and RoPE fallback kernels)."""
+def test_header_symbols_are_exported_at_abi_13():
+    """Every declared symbol resolves, and the library and the loader agree on ABI 13 (13: the single-kernel entries of the vision operand
+    producers and gathers, and the two host-only vision plans)."""
     hdr = open(os.path.join(ROOT, "include", "llava_reward_hip.h")).read()
     declared = set(re.findall(r"^(?:int|size_t|uint64_t|const char\*)\s+(lr_\w+)\(", hdr, flags=re.M))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     lib = _lib.load()                      # resolves every symbol; no compute without a GPU
-    assert lib.lr_abi_version() == _lib.LR_ABI_VERSION == 12
+    assert lib.lr_abi_version() == _lib.LR_ABI_VERSION == 13
     assert _lib.ModelDesc.struct_size.offset == 0
 
 
